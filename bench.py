@@ -11,6 +11,11 @@ synthetic feature maps at the BASELINE config-2 shapes (Swin-V2-B + HTS-AT), bf1
 data-parallel gradient all-reduce (N > 1) and an Adam step on the adapter parameters (the reference
 trains them with Adam, main_trans.py:276); weights change every step, so the MFMA-operand weight copies
 are re-made every step inside the timed region as well.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the diagnostics that take runs of their
+own: the host floor, the roofline / per-stage / GEMM-family figures, the CPU baseline and (data-parallel) the all-reduce A/B.
+--dump-outputs DIR writes what the last timed step computed (stage outputs, last-stage maps, the updated adapter parameters;
+fixed seeded samples of the large ones) as float32 DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -253,6 +258,36 @@ def cpu_baseline(backbone, max_seconds=30.0, b16_seconds=45.0):
                        f"as the reference's permuted-view path), thread count picked by a sweep")
 
 
+DUMP_OUT_ELEMS = 1 << 20          # per stage-output array (8 of them: 32 MB)
+DUMP_PARAM_ELEMS = 1 << 15        # per adapter parameter tensor (96 of them: at most 12.6 MB)
+
+
+def _sample(t, n, seed):
+    """float32 numpy copy of t (flattened), or of a fixed seeded sample of n of its elements (sorted indices)."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), n, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, outs, maps, params):
+    """What the last timed step hands back to its caller: the stage outputs (f_v, f_a) and the last stage's maps of the forward,
+    and the adapter parameters after the optimizer step."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for s, (fv, fa) in enumerate(outs):
+        arrays[f"out_stage{s}_visual"] = _sample(fv, DUMP_OUT_ELEMS, [s, 0])
+        arrays[f"out_stage{s}_audio"] = _sample(fa, DUMP_OUT_ELEMS, [s, 1])
+    arrays["map_visual"] = _sample(maps[0], DUMP_OUT_ELEMS, [99, 0])
+    arrays["map_audio"] = _sample(maps[1], DUMP_OUT_ELEMS, [99, 1])
+    arrays["params"] = np.concatenate([_sample(p, DUMP_PARAM_ELEMS, [i, 2]) for i, p in enumerate(params)])
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,6 +304,9 @@ def main():
     ap.add_argument("--blocks", action="store_true", help="harness B (SURVEY.md 8d / row f4): the frozen Swin-V2 half-blocks and HTS-AT blocks "
                     "(dgsct_amd/backbone.py, random-init, frozen, PyTorch-ROCm ops) inside the layer loop -- NOT the graded workload; the line "
                     "says so in config.workload")
+    ap.add_argument("--full", action="store_true", help="also the diagnostics beyond the headline: host floor, roofline / per-stage figures, "
+                    "CPU baseline, data-parallel all-reduce A/B (each can still be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--num-tokens", type=int, default=32, help="latent tokens per adapter (every reference launcher: <= 32 = the graded "
                     "workload; more -- the reference constructor's default is 87 -- runs the attentions on csrc/attn_wide.cpp)")
@@ -283,6 +321,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay one captured HIP graph per step instead of eager launches "
                     "(ROCm 7.2: replaying ~6000 nodes costs as much host time as launching them, so this is off by default)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -332,6 +372,7 @@ def main():
     feats, cots, mcots = make_inputs(stages, BT, dtype, device, seed=1 + rank)
 
     phase_ev = []                          # (start, end-of-forward, end-of-backward) events of the timed steps (--phases)
+    last = []                              # the forward results of the latest step, detached (--dump-outputs)
     from dgsct_amd.train import StackTrainer
     trainer = StackTrainer(stack, opt, reducer)      # the step logic the gloo world-2 test drives (tests/test_host_cpu.py)
     if args.blocks:
@@ -352,7 +393,8 @@ def main():
                 fv.grad = None
                 fa.grad = None
         else:
-            trainer.fwd_bwd(feats, cots, mcots)
+            outs, maps = trainer.fwd_bwd(feats, cots, mcots)
+        last[:] = [[(fv.detach(), fa.detach()) for fv, fa in outs], (maps[0].detach(), maps[1].detach())]
 
     def update():
         if opt is not None:
@@ -436,9 +478,12 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     host_ms = [round(x / args.steps * 1e3, 2) for x in host_parts]
     clips_per_s = per_gpu_batch * world / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:          # before the --full legs: they run further steps
+        dump_outputs(args.dump_outputs, last[0], last[1], params)
 
+    roofline_leg = args.full and not args.no_roofline
     host_floor = None
-    if rank == 0 and world == 1 and not use_graph and not args.no_roofline:
+    if rank == 0 and world == 1 and not use_graph and roofline_leg:
         # What the HOST needs per step: the same step on ONE clip (BT = 10: a sixteenth of the device work, every
         # launch still issued) is enqueue-bound -- its wall time per step is the host's floor for this schedule: Python + autograd +
         # ctypes + the library's launches and event forks.  Not part of `value`.
@@ -462,7 +507,7 @@ def main():
             host_floor = None
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline_leg:
         # dominant kernel family = the MFMA GEMM engine (gemm_kernel<...>): time every launch of two extra steps
         # with HIP events on the launch stream (the library records them itself: dgsct_prof_enable).
         lib = default_lib()
@@ -591,7 +636,7 @@ def main():
                         gemm_ms_per_step=round(gemm_ms / nprof, 3), heaviest_launch=heaviest,
                         step_frac_of_mfma_peak=step_block["frac_of_mfma_peak"], step=step_block, per_stage=per_stage, row_kernels=row_kernels)
     dp_info = None
-    if dp:
+    if dp and args.full:
         # what a driver log needs to diagnose a multi-GPU run without a second one: ranks RCCL really has, buckets launched from
         # the hooks, the spread of the per-rank step time, and the EXPOSED cost of the gradient exchange = this step against the
         # same steps with the exchange switched off (A/B inside this run, after the timed region; weights diverge, nothing reads them)
@@ -628,7 +673,7 @@ def main():
         if _l.test_tune("skip", -1) > 0 or _l.test_tune("noatomic", -1) > 0:
             raise SystemExit("bench.py: a what-if switch (dgsct_test_tune skip / noatomic) is set in this process: the step computed garbage, no line")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.backbone)
         line = dict(
             metric="adapter_fwd_bwd_clips_per_sec", value=round(clips_per_s, 2), unit="clips/s", n_gpus=world,

@@ -11,7 +11,7 @@ layout (q / k / v projections concatenated into ``attn.qkv``, ``query.bias`` -> 
 its output and input gradient to 1e-5 in fp32, and parameters / input / cotangent / output / input gradient are stored as the fixture
 (data only: no transformers or timm source is stored in this repo; the buffers that are pure functions of the geometry -- shift mask,
 offset table, pair index -- are rebuilt by the block's constructor and not stored).
-Run here:  python oracle/make_golden_swinv2.py
+Run here:  python oracle/make_golden_swinv2.py   (then --f64: the float64 results of the same layers, swinv2_block_f64.pt)
 """
 import importlib.util
 import os
@@ -87,5 +87,36 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def main_f64():
+    """tests/golden/swinv2_block_f64.pt: the HF layer of every case above (same seeds; its parameters must equal the committed fp32
+    fixture's bit for bit) evaluated in float64 on the fixture's input and cotangent -- output and input gradient in exact arithmetic up
+    to 1e-13 or so, the yardstick that does not depend on how the host's fp32 BLAS orders its sums (the fp32 results of two
+    implementations of this block are ~2e-5 apart in dx on some hosts, no nearer than fp32 rounding of the computation allows)."""
+    from transformers import Swinv2Config
+    from transformers.models.swinv2.modeling_swinv2 import Swinv2Layer
+    fx = torch.load(os.path.join(ROOT, "tests", "golden", "swinv2_block.pt"), weights_only=False)
+    out = {}
+    for name, (dim, res, heads, ws, shift) in CASES.items():
+        torch.manual_seed(21)
+        cfg = Swinv2Config(embed_dim=dim, depths=[1], num_heads=[heads], window_size=ws, mlp_ratio=4.0, hidden_dropout_prob=0.0,
+                           attention_probs_dropout_prob=0.0, drop_path_rate=0.0, hidden_act="gelu", layer_norm_eps=1e-5)
+        ref = Swinv2Layer(cfg, dim=dim, input_resolution=(res, res), num_heads=heads, shift_size=shift).eval()
+        with torch.no_grad():
+            for p in ref.parameters():
+                p.add_(0.1 * torch.randn_like(p))
+        sd = to_timm_names(ref.state_dict())
+        assert sd.keys() == fx[name]["state"].keys() and all(torch.equal(sd[k], fx[name]["state"][k]) for k in sd), name
+        ref = ref.double()
+        xr = fx[name]["x"].double().requires_grad_(True)
+        yr = ref(xr, (res, res))[0]
+        yr.backward(fx[name]["cot"].double())
+        print(f"{name:14s} fp32 fixture vs float64:  |y| {(fx[name]['y'].double() - yr).abs().max().item():.2e}   "
+              f"|dx| {(fx[name]['dx'].double() - xr.grad).abs().max().item():.2e}")
+        out[name] = dict(y=yr.detach(), dx=xr.grad.detach())
+    path = os.path.join(ROOT, "tests", "golden", "swinv2_block_f64.pt")
+    torch.save(out, path)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    main_f64() if "--f64" in sys.argv else main()

@@ -52,14 +52,22 @@ def _swin_block(fx, **kw):
 def test_swinv2_block_matches_the_independent_implementation_fixture(name):
     """timm 0.6.12 (the reference's Swin-V2 blocks) is absent: parity against timm stays unpinned.  This pins `SwinV2Block` against an
     INDEPENDENT implementation of the same published block -- Hugging Face transformers' `Swinv2Layer`, run by oracle/make_golden_swinv2.py
-    with its parameters renamed to timm's layout -- output and input gradient to 1e-5 in fp32 (plain / shifted 12 x 12 windows on a
-    24 x 24 map, the map as one 6 x 6 window, shifted 8 x 8 windows)."""
+    with its parameters renamed to timm's layout -- in float64 (oracle/make_golden_swinv2.py --f64) output and input gradient to 1e-10;
+    in fp32 the output to 1e-5 and the input gradient no further from the float64 result than twice the HF layer's own fp32 gradient
+    (fp32 rounding alone puts dx ~2e-5 from exact here, and where on that scale it lands depends on the host's BLAS) -- plain / shifted
+    12 x 12 windows on a 24 x 24 map, the map as one 6 x 6 window, shifted 8 x 8 windows."""
     fx = _swin_cases()[name]
+    ref = torch.load(os.path.join(ROOT, "tests", "golden", "swinv2_block_f64.pt"), weights_only=False)[name]
+    x64 = fx["x"].double().requires_grad_(True)
+    y64 = _swin_block(fx, fused=False).double()(x64)
+    y64.backward(fx["cot"].double())
+    assert (y64 - ref["y"]).abs().max() < 1e-10 and (x64.grad - ref["dx"]).abs().max() < 1e-10
     blk = _swin_block(fx, fused=False)
     x = fx["x"].clone().requires_grad_(True)
     y = blk(x)
     y.backward(fx["cot"])
-    assert (y - fx["y"]).abs().max() < 1e-5 and (x.grad - fx["dx"]).abs().max() < 1e-5
+    assert (y - fx["y"]).abs().max() < 1e-5
+    assert (x.grad.double() - ref["dx"]).abs().max() <= 2 * (fx["dx"].double() - ref["dx"]).abs().max()
     # the two halves as the AVE loop calls them (net_trans.py:894, :903) compose to the block
     h = fx["x"] + blk.attn_branch(fx["x"])
     assert torch.allclose(h + blk.mlp_branch(h), y.detach(), atol=1e-6)

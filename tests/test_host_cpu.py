@@ -688,3 +688,31 @@ def test_pair_node_in_eval_mode_without_grad_and_over_two_backward_passes():
     assert set(g0) == set(g1) and len(g0) >= len(fx["grads"])
     for k in g0:
         assert rel_err(g1[k], g0[k]) < 1e-5, k
+
+
+def test_bench_dump_outputs_is_float32_and_reproducible(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 arrays named after what the step returns, the same fixed sample of an oversized array
+    on every call (two builds are compared array by array)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_OUT_ELEMS", 100)
+    monkeypatch.setattr(bench, "DUMP_PARAM_ELEMS", 7)
+    g = torch.Generator().manual_seed(0)
+    outs = [(torch.randn(2, 9, 8, generator=g).bfloat16(), torch.randn(2, 4, 4, generator=g).bfloat16()) for _ in range(4)]
+    maps = (torch.randn(2, 1, 9, generator=g), torch.randn(2, 1, 4, generator=g))
+    params = [torch.nn.Parameter(torch.randn(n, generator=g)) for n in (5, 50)]
+    bench.dump_outputs(str(tmp_path / "a"), outs, maps, params)
+    bench.dump_outputs(str(tmp_path / "b"), outs, maps, params)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted([f"out_stage{s}_{m}.npy" for s in range(4) for m in ("visual", "audio")] +
+                           ["map_visual.npy", "map_audio.npy", "params.npy"])
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+    v = np.load(tmp_path / "a" / "out_stage0_visual.npy")
+    assert v.shape == (100,) and np.isin(v, outs[0][0].float().numpy().ravel()).all()          # a sample of 144 elements
+    assert np.array_equal(np.load(tmp_path / "a" / "out_stage0_audio.npy"), outs[0][1].float().numpy().ravel())
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.shape == (12,) and np.array_equal(p[:5], params[0].detach().numpy())
+    assert np.isin(p[5:], params[1].detach().numpy()).all() and len(set(p[5:].tolist())) == 7

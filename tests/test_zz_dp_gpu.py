@@ -77,7 +77,7 @@ def test_bench_contract_last_stdout_line_is_the_json_line():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-roofline", "--force-dp", "--batch", "2"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -87,3 +87,34 @@ def test_bench_contract_last_stdout_line_is_the_json_line():
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
     assert "workload" in d["config"] and "model" not in d["config"]
+    assert d["dp"]["rccl_ranks"] == 1                          # --full: the data-parallel diagnostics and their A/B leg ran
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline without the diagnostic legs; --dump-outputs
+    writes the last timed step's results as finite float32 .npy files, 64 MB at most."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["metric"] == "adapter_fwd_bwd_clips_per_sec" and d["unit"] == "clips/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["config"]["host_floor_ms_per_step"] is None
+    names = sorted(f.name for f in out.iterdir())
+    assert names == sorted([f"out_stage{s}_{m}.npy" for s in range(4) for m in ("visual", "audio")] +
+                           ["map_visual.npy", "map_audio.npy", "params.npy"])
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    for f in out.iterdir():
+        a = np.load(f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f.name
