@@ -130,7 +130,11 @@ class Lib:
         c.dgsct_layer_norm_scratch_floats.restype = C.c_int64
         c.dgsct_layer_norm_forward.argtypes = [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 5
         c.dgsct_layer_norm_backward.argtypes = [C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 5
-        if c.dgsct_version() != 100:
+        # optional (include/dgsct.h): the table-gradient backward of the window attention; the host emulation of the CPU tests lacks it
+        self._wattn_tables = getattr(c, "dgsct_window_attn_backward_tables", None)
+        if self._wattn_tables is not None:
+            self._wattn_tables.argtypes = [C.c_int] * 9 + [C.c_void_p] * 10
+        if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
     # ------------------------------------------------------------------
@@ -208,6 +212,18 @@ class Lib:
 
     def window_attn_backward(self, geom, qkv, bm, scale, out, lse, dout, dqkv, stream, flags=0):
         self._check(self.c.dgsct_window_attn_backward_ex(*geom, flags, qkv, bm, scale, out, lse, dout, dqkv, stream), "dgsct_window_attn_backward")
+
+    @property
+    def has_window_attn_tables(self) -> bool:
+        """whether this library exports dgsct_window_attn_backward_tables (bias-table / logit-scale gradients of trainable blocks)"""
+        return self._wattn_tables is not None
+
+    def window_attn_backward_tables(self, geom, qkv, bm, scale, out, lse, dout, dqkv, dbm, dscale, stream, flags=0):
+        """dqkv as window_attn_backward, plus dbm [nwm, heads, n, n] / dscale [heads] (fp32, zeroed by the call; None = not wanted)"""
+        if self._wattn_tables is None:
+            raise RuntimeError(f"dg-sct_amd: {self.path} does not export dgsct_window_attn_backward_tables")
+        self._check(self._wattn_tables(*geom, flags, qkv, bm, scale, out, lse, dout, dqkv, dbm, dscale, stream),
+                    "dgsct_window_attn_backward_tables")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

@@ -89,6 +89,28 @@ def _ln(norm: nn.LayerNorm, x: torch.Tensor, residual: Optional[torch.Tensor] = 
     return ops.layer_norm(x, c[1], c[2], norm.eps, residual, lib)
 
 
+def _linear(lin: nn.Linear, x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`lin(x)` in x's dtype: parameters of another dtype (fp32 masters under a block's `compute_dtype`) go through a differentiable
+    per-forward cast, so their gradients arrive in fp32"""
+    w = lin.weight if weight is None else weight
+    b = lin.bias if bias is None else bias
+    if w.dtype != x.dtype:
+        w = w.to(x.dtype)
+        b = b.to(x.dtype) if b is not None else None
+    return F.linear(x, w, b)
+
+
+def _norm(norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
+    """`norm(x)` of the ATen path in x's dtype (fp32 masters under `compute_dtype`: a differentiable cast of weight / bias)"""
+    if norm.weight.dtype == x.dtype:
+        return norm(x)
+    return F.layer_norm(x, norm.normalized_shape, norm.weight.to(x.dtype), norm.bias.to(x.dtype), norm.eps)
+
+
+def _compute(x: torch.Tensor, compute_dtype: Optional[torch.dtype]) -> torch.Tensor:
+    return x if compute_dtype is None or x.dtype == compute_dtype else x.to(compute_dtype)
+
+
 class _Mlp(nn.Module):
     def __init__(self, dim: int, hidden: int):
         super().__init__()
@@ -97,7 +119,7 @@ class _Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden, dim)
 
     def forward(self, x):
-        return self.fc2(self.act(self.fc1(x)))
+        return _linear(self.fc2, self.act(_linear(self.fc1, x)))
 
 
 class _WindowAttentionV1(nn.Module):
@@ -114,12 +136,19 @@ class _WindowAttentionV1(nn.Module):
         self.proj = nn.Linear(dim, dim)
 
     def _tables(self, mask):
-        """frozen per-block tables of the fused kernel (csrc/wattn.hip): bm [1 | nW, heads, n, n] = relative-position bias (+ shift mask),
-        scale [heads]; fp32, rebuilt only when the bias table changes (it is frozen in the reference: main_trans.py:211-256)"""
+        """tables of the fused kernel (csrc/wattn.hip): bm [1 | nW, heads, n, n] = relative-position bias (+ shift mask), scale [heads]; fp32.
+        Frozen (the reference freezes the block: main_trans.py:211-256): rebuilt only when the bias table changes.  Trainable (AVS-S4 trains
+        the HTS-AT blocks: avs_s4/train.py:145-163): the same gather, differentiable and rebuilt on every forward, so the kernel's dbm reaches
+        relative_position_bias_table as the scatter-add of the gather's backward"""
         tab = self.relative_position_bias_table
+        n, h = self.window_size[0] * self.window_size[1], self.num_heads
+        if torch.is_grad_enabled() and tab.requires_grad:
+            bm = tab[self.relative_position_index.reshape(-1)].reshape(n, n, h).permute(2, 0, 1).float()[None]
+            if mask is not None:
+                bm = bm + mask.float()[:, None]
+            return bm.contiguous(), torch.full((h,), float(self.scale), dtype=torch.float32, device=tab.device)
         key = (tab._version, tab.device, mask is None)
         if getattr(self, "_tab_cache", (None,))[0] != key:
-            n, h = self.window_size[0] * self.window_size[1], self.num_heads
             with torch.no_grad():
                 bm = tab[self.relative_position_index.reshape(-1)].reshape(n, n, h).permute(2, 0, 1).float()[None]
                 if mask is not None:
@@ -132,13 +161,13 @@ class _WindowAttentionV1(nn.Module):
         window partition / cyclic shift by address arithmetic (no roll / partition copies, no [windows, heads, n, n] tensor), then proj"""
         from . import ops
         bm, scale = self._tables(mask)
-        o = ops.window_attention(self.qkv(y), bm, scale, H, W, self.window_size[0], shift, self.num_heads, lib)
-        return self.proj(o)
+        o = ops.window_attention(_linear(self.qkv, y), bm, scale, H, W, self.window_size[0], shift, self.num_heads, lib)
+        return _linear(self.proj, o)
 
     def forward(self, x, mask=None):
         Bw, n, C = x.shape
         h = self.num_heads
-        q, k, v = self.qkv(x).reshape(Bw, n, 3, h, C // h).permute(2, 0, 3, 1, 4)
+        q, k, v = _linear(self.qkv, x).reshape(Bw, n, 3, h, C // h).permute(2, 0, 3, 1, 4)
         logits = (q * self.scale) @ k.transpose(-2, -1)
         bias = self.relative_position_bias_table[self.relative_position_index.reshape(-1)].reshape(n, n, h).permute(2, 0, 1)
         logits = logits + bias.to(logits.dtype)[None]
@@ -146,20 +175,25 @@ class _WindowAttentionV1(nn.Module):
             nW = mask.shape[0]
             logits = (logits.reshape(Bw // nW, nW, h, n, n) + mask.to(logits.dtype)[None, :, None]).reshape(Bw, h, n, n)
         attn = logits.softmax(-1)
-        return self.proj((attn @ v).transpose(1, 2).reshape(Bw, n, C)), attn
+        return _linear(self.proj, (attn @ v).transpose(1, 2).reshape(Bw, n, C)), attn
 
 
 class HTSATBlock(nn.Module):
     """``SwinTransformerBlock`` of htsat.py:135-251 (LayerNorm before the MLP, no drop-path / dropout: the frozen model runs them at
-    0): ``forward(x [B, H*W, C]) -> (x, attn)`` like the reference call ``f_a, _ = blk_a(f_a)``."""
+    0): ``forward(x [B, H*W, C]) -> (x, attn)`` like the reference call ``f_a, _ = blk_a(f_a)``.
+
+    Trainable as AVS-S4 trains it (``avs_s4/train.py:145-163``): with parameters that require grad the fused path returns a gradient
+    for every one of them, the bias table's included (the kernel's table-gradient backward).  ``compute_dtype=torch.bfloat16`` with fp32
+    parameters: the block computes in bf16 (through the fused kernels on the GPU) on differentiable per-forward casts of its weights, so
+    fp32 master parameters train -- as ``VisualAdapter(compute_dtype=)`` does for the adapters; the output is in compute_dtype."""
 
     def __init__(self, dim: int, input_resolution: Tuple[int, int], num_heads: int, window_size: int = 8, shift_size: int = 0,
-                 mlp_ratio: float = 4.0, fused: Optional[bool] = None, lib=None):
+                 mlp_ratio: float = 4.0, fused: Optional[bool] = None, lib=None, compute_dtype: Optional[torch.dtype] = None):
         super().__init__()
         self.dim, self.input_resolution, self.num_heads = dim, tuple(input_resolution), num_heads
         # fused: None = the HIP window-attention kernel whenever it applies (bf16 on the GPU), False = the ATen formulation (the one pinned
         # bit-exactly to the reference class on the CPU); lib: a C-ABI instance other than the default (the host emulation of the CPU tests)
-        self.fused, self._lib = fused, lib
+        self.fused, self._lib, self.compute_dtype = fused, lib, compute_dtype
         if min(self.input_resolution) <= window_size:                          # a window as large as the map: one window, no shift
             shift_size, window_size = 0, min(self.input_resolution)
         self.window_size, self.shift_size = window_size, shift_size
@@ -178,12 +212,13 @@ class HTSATBlock(nn.Module):
     def forward(self, x):
         H, W = self.input_resolution
         B, L, C = x.shape
+        x = _compute(x, self.compute_dtype)
         if self._use_fused(x):
             # fused window attention (csrc/wattn.hip): the attention probabilities are never materialised, so the second result of the
             # reference call `f_a, _ = blk_a(f_a)` (net_trans.py:897, discarded there) is None on this path
             x = x + self.attn.forward_map(_ln(self.norm1, x, None, self._lib), H, W, self.shift_size, self.attn_mask, self._lib)
             return x + self.mlp(_ln(self.norm2, x, None, self._lib)), None
-        y = self.norm1(x).reshape(B, H, W, C)
+        y = _norm(self.norm1, x).reshape(B, H, W, C)
         s = self.shift_size
         if s:
             y = torch.roll(y, shifts=(-s, -s), dims=(1, 2))
@@ -192,7 +227,7 @@ class HTSATBlock(nn.Module):
         if s:
             y = torch.roll(y, shifts=(s, s), dims=(1, 2))
         x = x + y.reshape(B, L, C)
-        return x + self.mlp(self.norm2(x)), attn
+        return x + self.mlp(_norm(self.norm2, x)), attn
 
 
 class _WindowAttentionV2(nn.Module):
@@ -216,11 +251,21 @@ class _WindowAttentionV2(nn.Module):
         self.proj = nn.Linear(dim, dim)
 
     def _tables(self, mask):
-        """frozen tables of the fused kernel: bm = 16 sigmoid(cpb_mlp(offsets))[pair] (+ shift mask), scale = exp(min(logit_scale, log 100))"""
+        """tables of the fused kernel: bm = 16 sigmoid(cpb_mlp(offsets))[pair] (+ shift mask), scale = exp(min(logit_scale, log 100)).
+        Frozen: cached until a parameter they come from changes.  Trainable: built differentiably on every forward (no cache), so the
+        kernel's dbm / dscale reach cpb_mlp.* and logit_scale through autograd"""
         w = self.cpb_mlp[0].weight
-        key = (w._version, self.cpb_mlp[2].weight._version, self.logit_scale._version, w.device, mask is None)
+        n, h = self.window_size[0] * self.window_size[1], self.num_heads
+        srcs = list(self.cpb_mlp.parameters()) + [self.logit_scale]
+        if torch.is_grad_enabled() and any(p_.requires_grad for p_ in srcs):
+            table = self.cpb_mlp(self.relative_coords_table.to(w.dtype)).reshape(-1, h).float()
+            bm = (16 * torch.sigmoid(table[self.relative_position_index.reshape(-1)].reshape(n, n, h).permute(2, 0, 1)))[None]
+            if mask is not None:
+                bm = bm + mask.float()[:, None]
+            scale = torch.clamp(self.logit_scale.float(), max=math.log(100.0)).exp().reshape(h)
+            return bm.contiguous(), scale.contiguous()
+        key = (tuple(p_._version for p_ in srcs), w.device, mask is None)
         if getattr(self, "_tab_cache", (None,))[0] != key:
-            n, h = self.window_size[0] * self.window_size[1], self.num_heads
             with torch.no_grad():
                 table = self.cpb_mlp(self.relative_coords_table.to(w.dtype)).reshape(-1, h).float()
                 bm = (16 * torch.sigmoid(table[self.relative_position_index.reshape(-1)].reshape(n, n, h).permute(2, 0, 1)))[None]
@@ -238,15 +283,15 @@ class _WindowAttentionV2(nn.Module):
         B, L, C = y.shape
         h = self.num_heads
         bias3 = torch.cat([self.q_bias, torch.zeros_like(self.v_bias), self.v_bias])
-        qkv = F.linear(y, self.qkv.weight, bias3)
+        qkv = _linear(self.qkv, y, bias=bias3)
         bm, scale = self._tables(mask)
-        return self.proj(ops.window_attention(qkv, bm, scale, H, W, self.window_size[0], shift, h, lib, cosine=True))
+        return _linear(self.proj, ops.window_attention(qkv, bm, scale, H, W, self.window_size[0], shift, h, lib, cosine=True))
 
     def forward(self, x, mask=None):
         Bw, n, C = x.shape
         h = self.num_heads
         bias3 = torch.cat([self.q_bias, torch.zeros_like(self.v_bias), self.v_bias])
-        q, k, v = F.linear(x, self.qkv.weight, bias3).reshape(Bw, n, 3, h, C // h).permute(2, 0, 3, 1, 4)
+        q, k, v = _linear(self.qkv, x, bias=bias3).reshape(Bw, n, 3, h, C // h).permute(2, 0, 3, 1, 4)
         logits = F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-2, -1)
         logits = logits * torch.clamp(self.logit_scale, max=math.log(100.0)).exp().to(logits.dtype)
         table = self.cpb_mlp(self.relative_coords_table.to(self.cpb_mlp[0].weight.dtype)).reshape(-1, h)
@@ -255,18 +300,19 @@ class _WindowAttentionV2(nn.Module):
         if mask is not None:
             nW = mask.shape[0]
             logits = (logits.reshape(Bw // nW, nW, h, n, n) + mask.to(logits.dtype)[None, :, None]).reshape(Bw, h, n, n)
-        return self.proj((logits.softmax(-1) @ v).transpose(1, 2).reshape(Bw, n, C))
+        return _linear(self.proj, (logits.softmax(-1) @ v).transpose(1, 2).reshape(Bw, n, C))
 
 
 class SwinV2Block(nn.Module):
     """timm 0.6.12 ``SwinTransformerV2Block`` with its two residual branches exposed the way ``net_trans.py:894, 903`` uses them:
-    ``attn_branch(x) = norm1(_attn(x))`` and ``mlp_branch(x) = norm2(mlp(x))`` (post-norm; drop-path 0 in the frozen model)."""
+    ``attn_branch(x) = norm1(_attn(x))`` and ``mlp_branch(x) = norm2(mlp(x))`` (post-norm; drop-path 0 in the frozen model).
+    Trainable and ``compute_dtype`` as ``HTSATBlock``: cpb_mlp.* and logit_scale get their gradients on the fused path too."""
 
     def __init__(self, dim: int, input_resolution: Tuple[int, int], num_heads: int, window_size: int = 12, shift_size: int = 0,
-                 mlp_ratio: float = 4.0, fused: Optional[bool] = None, lib=None):
+                 mlp_ratio: float = 4.0, fused: Optional[bool] = None, lib=None, compute_dtype: Optional[torch.dtype] = None):
         super().__init__()
         self.dim, self.input_resolution, self.num_heads = dim, tuple(input_resolution), num_heads
-        self.fused, self._lib = fused, lib                                     # (as HTSATBlock)
+        self.fused, self._lib, self.compute_dtype = fused, lib, compute_dtype   # (as HTSATBlock)
         if min(self.input_resolution) <= window_size:
             shift_size, window_size = 0, min(self.input_resolution)
         self.window_size, self.shift_size = window_size, shift_size
@@ -303,15 +349,17 @@ class SwinV2Block(nn.Module):
 
     def attn_branch(self, x, add_residual: bool = False):
         """norm1(_attn(x)); add_residual: the whole line `x + norm1(_attn(x))` of net_trans.py:894 (one kernel with the fused LayerNorm)"""
+        x = _compute(x, self.compute_dtype)
         if self._use_fused(x):
             return _ln(self.norm1, self._attn(x), x if add_residual else None, self._lib)
-        y = self.norm1(self._attn(x))
+        y = _norm(self.norm1, self._attn(x))
         return x + y if add_residual else y
 
     def mlp_branch(self, x, add_residual: bool = False):
+        x = _compute(x, self.compute_dtype)
         if self._use_fused(x):
             return _ln(self.norm2, self.mlp(x), x if add_residual else None, self._lib)
-        y = self.norm2(self.mlp(x))
+        y = _norm(self.norm2, self.mlp(x))
         return x + y if add_residual else y
 
     def forward(self, x):
@@ -327,20 +375,33 @@ _HTSAT_HEADS = {96: 4, 192: 8, 384: 16, 768: 32}
 class FrozenBlocks(nn.Module):
     """The frozen blocks that sit beside the adapter positions of an ``AdapterStack`` (one Swin-V2 block and one HTS-AT block per
     adapter layer; shifted windows on every second block of a stage, as the backbones alternate), randomly initialised -- no
-    pretrained weights exist offline -- and frozen.  ``vis_block`` / ``aud_block`` are the callables ``AdapterStack.forward`` takes."""
+    pretrained weights exist offline -- and frozen.  ``vis_block`` / ``aud_block`` are the callables ``AdapterStack.forward`` takes.
 
-    def __init__(self, stages: Sequence[Dict[str, int]], dtype: torch.dtype = torch.bfloat16, fused: Optional[bool] = None):
+    ``train_htsat=True`` is AVS-S4's rule (``avs_s4/train.py:145-163``: only ``'ViT'`` / ``'swin'`` frozen): the HTS-AT blocks keep fp32,
+    trainable parameters and compute in ``dtype`` (``compute_dtype``); the Swin-V2 blocks stay frozen in ``dtype``."""
+
+    def __init__(self, stages: Sequence[Dict[str, int]], dtype: torch.dtype = torch.bfloat16, fused: Optional[bool] = None,
+                 train_htsat: bool = False):
         super().__init__()
         vis, aud = [], []
+        cd = dtype if train_htsat and dtype != torch.float32 else None
         for s in stages:
             rv, ra = int(round(math.sqrt(s["Nv"]))), int(round(math.sqrt(s["Na"])))
             for i in range(s["layers"]):
                 vis.append(SwinV2Block(s["Cv"], (rv, rv), _SWIN_HEADS[s["Cv"]], window_size=12, shift_size=0 if i % 2 == 0 else 6, fused=fused))
-                aud.append(HTSATBlock(s["Ca"], (ra, ra), _HTSAT_HEADS[s["Ca"]], window_size=8, shift_size=0 if i % 2 == 0 else 4, fused=fused))
+                aud.append(HTSATBlock(s["Ca"], (ra, ra), _HTSAT_HEADS[s["Ca"]], window_size=8, shift_size=0 if i % 2 == 0 else 4, fused=fused,
+                                      compute_dtype=cd))
         self.vis, self.aud = nn.ModuleList(vis), nn.ModuleList(aud)
-        self.to(dtype)
-        for p in self.parameters():
+        self.train_htsat = bool(train_htsat)
+        if train_htsat:
+            self.vis.to(dtype)
+            self.aud.to(torch.float32)
+        else:
+            self.to(dtype)
+        for p in self.vis.parameters():
             p.requires_grad_(False)
+        for p in self.aud.parameters():
+            p.requires_grad_(self.train_htsat)
 
     def vis_block(self, idx: int, half: int, f_v: torch.Tensor) -> torch.Tensor:
         """the residual branch of Swin block `idx`: half 0 = window attention, half 1 = MLP (net_trans.py:894 / :903)"""

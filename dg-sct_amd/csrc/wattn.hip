@@ -1,4 +1,5 @@
-// Fused window attention of the FROZEN backbone blocks either side of the adapter calls:
+// Fused window attention of the backbone blocks either side of the adapter calls, frozen (the AVE rule) or
+// trainable (AVS-S4 trains the HTS-AT blocks: the table-gradient backward below also returns d bm and d scale):
 //   HTS-AT  WindowAttention.forward   /root/reference DG-SCT/AVE/nets/htsat.py:50-132   (called from the block, :135-251)
 //   Swin-V2 window attention of the timm block the AVE loop calls at net_trans.py:894   (cosine form: q, k arrive normalised)
 //
@@ -10,7 +11,7 @@
 //   * the window partition and the cyclic shift are ADDRESS ARITHMETIC: q, k, v rows are gathered straight from the [B, H*W, 3C] output of
 //     the qkv projection applied to the un-partitioned map (a Linear commutes with the token permutation) and O rows land at their map
 //     positions -- no roll, no partition tensors;
-//   * relative-position bias and shift mask are ONE frozen fp32 table bm[window type][head][n][n], added to the logits in registers;
+//   * relative-position bias and shift mask are ONE fp32 table bm[window type][head][n][n], added to the logits in registers;
 //   * logits^T[j][i] = k_j . q_i is formed TRANSPOSED (v_mfma_f32_32x32x16_bf16, A = K rows, B = Q rows), so the softmax axis j runs along a
 //     lane's accumulator registers (+ lane ^ 32): no cross-lane softmax, and the probability tile in registers IS the B operand of
 //     O^T = V^T P^T (the contraction index of an MFMA may be permuted as long as both operands agree: V^T is transpose-read from LDS in the
@@ -20,11 +21,14 @@
 //     backward's row reductions (flash-attention form).
 // One workgroup per (frame, window, head); its wavefronts split the 32-row tiles.  bf16 operands, fp32 accumulation / softmax.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
+#include <type_traits>
 #include "device_util.h"
 #include "mma_tile.h"
 #include "err.h"
 #include "prims.h"
+#include "../../include/dgsct.h"
 
 namespace dgsct {
 namespace {
@@ -253,22 +257,30 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_fwd_k(const W
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------
-template <int NPAD>
-__global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const WArgs p) {
-  constexpr int WIMG = NPAD * WP, WMAXT = NPAD / 32;
-  __shared__ __attribute__((aligned(16))) char smem[4 * WIMG];
-  __shared__ int rows[NPAD];
-  __shared__ float sL[NPAD], sD[NPAD], sInv[2 * NPAD];       // sInv: 1 / |q_i|, 1 / |k_j| (cosine mode)
+// Table-gradient variant (TAB, trainable blocks): besides dqkv it sums dS = P o (dP - rowsum(P o dP)), the gradient of the logits, into
+//   dbm[t][h][i][j]  = sum over frames b and windows w with w % nwm == t of dS[i][j]        (i, j < n)
+//   dscale[h]        = sum over b, w, i, j of dS[i][j] * (q_i . k_j)                        (the dot the logits were formed from)
+// taken from the two passes that exist (dscale and the row sums r_i of the i-owner pass, dbm in the j-owner pass; no third recompute
+// pass; dS corrected by r_i as pass 1 explains).  A workgroup of this variant owns ONE destination
+// (t, h) and loops over G window instances that share it (frames, and for nwm = 1 the windows of a frame), adding its dS tiles into an
+// n x n fp32 slab in LDS (dynamic; every (i, j) has exactly one owning lane, so plain read-add-write); one global float atomic add per
+// slab element per workgroup at the end.  Flushing every instance's n^2 partial would cost about as much as the whole backward
+// (671 MB of float atomics at HTS-AT stage 0, B = 160); with G >= 8 it is an eighth or less.
+struct WTab {
+  float* dbm;                                   // [nwm][heads][n][n] fp32, zeroed by the launcher (NULL: not wanted)
+  float* dscale;                                // [heads] fp32, zeroed by the launcher (NULL: not wanted)
+  int G, R, nper;                               // instances per workgroup, instances per destination (B * nW / nwm), windows per frame per type
+};
+struct WArgsT : WArgs { WTab tab; };
+template <bool TAB>
+using WBwdArgs = typename std::conditional<TAB, WArgsT, WArgs>::type;
+
+// one window instance (frame b, window w, head): dQ, dK, dV rows; TAB: + the slab / dscale partials
+template <int NPAD, bool TAB, class A>
+__device__ __forceinline__ void wattn_bwd_win(const A& p, int b, int w, int head, char* smem, int* rows, float* sL, float* sD, float* sInv,
+                                              float* sR, float* slab, float& dsc) {
+  constexpr int WIMG = NPAD * WP;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = blockDim.x >> 6;
-  // XCD-aware order: workgroup g runs on XCD g % 8 (each with its own L2).  Window instances k = b * nW + w go round-robin over the XCDs and
-  // the heads of one instance stay together on its XCD: (a) two heads share every 128-byte line of the qkv rows (64-byte pieces at head width
-  // 32) -- the second finds it in L2; (b) an XCD only ever sees the window types w = k % 8 (mod nW), i.e. an eighth of a shifted block's
-  // bias / mask table (5.3 MB at 16 window types x 4 heads of 144 x 144: more than one L2 holds; with every window type on every XCD the
-  // backward of the stage-0 Swin block took 940 us instead of 690).  Measured against the plain order: -3 ... -45 % per launch.
-  const int kl = (int)(blockIdx.x >> 3) / p.heads, k = kl * 8 + (int)(blockIdx.x & 7);
-  const int item = k * p.heads + (int)(blockIdx.x >> 3) - kl * p.heads;
-  if (k >= p.items / p.heads) return;
-  const int head = item % p.heads, w = (item / p.heads) % p.nW, b = item / (p.heads * p.nW);
   const int wy = w / p.nwx, wx = w - wy * p.nwx;
   const int n = p.n, nt = (n + 31) / 32, npad = nt * 32, L = p.H * p.W, C = p.heads * p.hd;
   for (int t = tid; t < npad; t += blockDim.x) rows[t] = tok_row(p, wy, wx, t < n ? t : n - 1);
@@ -316,6 +328,7 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const W
     const wbf8 q0 = frag_km(sQ, it * 32, 0, lane), q1 = frag_km(sQ, it * 32, 1, lane);
     const wbf8 g0 = frag_km(sG, it * 32, 0, lane), g1 = frag_km(sG, it * 32, 1, lane);
     const float li = sL[ic], di = sD[ic];
+    float ra = 0.f, rs = 0.f, rm = 0.f;                      // TAB: sum_j dS s, sum_j dS, sum_j P s of row i (this lane's half of the j's)
     wf16 o; zero16(o);
 #pragma unroll 1                                             // (unrolled over 5 tiles the compiler kept every tile's fragments and temporaries
     for (int jt = 0; jt < nt; ++jt) {                        //  live: 482 VGPRs, one wavefront per SIMD)
@@ -335,6 +348,7 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const W
           const int r = 4 * q + e;
           const float pr = (j0 < n && i < n) ? __expf(s[r] * sc + be[e] - li) : 0.f;
           ds[r] = pr * (dp[r] - di);
+          if constexpr (TAB) { ra += ds[r] * s[r]; rs += ds[r]; rm += pr * s[r]; }
         }
       }
       o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_acc(sK, jt * 32, 0, lane), regs8(ds), o, 0, 0, 0);
@@ -342,7 +356,16 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const W
     }
     if (p.cosine) store_rows_T_cos(o, sc, sQ, sInv, dq, 3L * C, 0, rows, it * 32, n, p.hd, lane);
     else store_rows_T(o, sc, dq, 3L * C, 0, rows, it * 32, n, p.hd, lane);
+    if constexpr (TAB) {
+      // D_i = dO_i . O_i is formed from the bf16-rounded O; sum_j dS_ij = rowsum(P o dP) - D_i = r_i is what that rounding left over.
+      // The table gradients take dS' = dS - P r_i (= P o (dP - rowsum(P o dP)), the exact form): summed over thousands of (i, j), the
+      // uncorrected r_i terms do not cancel (dscale of a 36-token window was 2 x further from fp32 than the bf16 ATen evaluation).
+      // dqkv keeps dS, bit for bit the frozen variant's.  sum_j dS'_ij s_ij = ra - r_i rm.
+      ra += xor32(ra); rs += xor32(rs); rm += xor32(rm);
+      if (lane < 32 && i < n) { sR[i] = rs; dsc += ra - rs * rm; }
+    }
   }
+  if constexpr (TAB) __syncthreads();                        // r_i of every row before the j-owner pass
   // pass 2 (j-owner; logits[i][j]): dK and dV rows
   for (int jt = wave; jt < nt; jt += nwv) {
     const int j = jt * 32 + (lane & 31), jc = j < n ? j : n - 1;
@@ -364,6 +387,15 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const W
         pr[r] = e;
         ds[r] = e * (dp[r] - sD[ic]);
       }
+      if constexpr (TAB) {                                   // slab += dS' = dS - P r_i (see pass 1)
+        if (slab && j < n) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int i = it * 32 + mt_row(r, lane);
+            if (i < n) slab[i * n + j] += ds[r] - pr[r] * sR[i];
+          }
+        }
+      }
       ov = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_acc(sG, it * 32, 0, lane), regs8(pr), ov, 0, 0, 0);
       ov = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_acc(sG, it * 32, 1, lane), regs8(pr + 8), ov, 0, 0, 0);
       ok = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_acc(sQ, it * 32, 0, lane), regs8(ds), ok, 0, 0, 0);
@@ -372,6 +404,54 @@ __global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, 4) void wattn_bwd_k(const W
     if (p.cosine) store_rows_T_cos(ok, sc, sK, sInv + npad, dq, 3L * C, C, rows, jt * 32, n, p.hd, lane);
     else store_rows_T(ok, sc, dq, 3L * C, C, rows, jt * 32, n, p.hd, lane);
     store_rows_T(ov, 1.f, dq, 3L * C, 2 * C, rows, jt * 32, n, p.hd, lane);
+  }
+}
+
+template <int NPAD, bool TAB>                                 // (TAB: the slab, not the registers, bounds the workgroups per CU)
+__global__ __launch_bounds__(NPAD <= 64 ? 128 : 320, TAB ? 2 : 4) void wattn_bwd_k(const WBwdArgs<TAB> p) {
+  constexpr int WIMG = NPAD * WP, WMAXT = NPAD / 32;
+  __shared__ __attribute__((aligned(16))) char smem[4 * WIMG];
+  __shared__ int rows[NPAD];
+  __shared__ float sL[NPAD], sD[NPAD], sInv[2 * NPAD];       // sInv: 1 / |q_i|, 1 / |k_j| (cosine mode)
+  if constexpr (!TAB) {
+    // XCD-aware order: workgroup g runs on XCD g % 8 (each with its own L2).  Window instances k = b * nW + w go round-robin over the XCDs and
+    // the heads of one instance stay together on its XCD: (a) two heads share every 128-byte line of the qkv rows (64-byte pieces at head width
+    // 32) -- the second finds it in L2; (b) an XCD only ever sees the window types w = k % 8 (mod nW), i.e. an eighth of a shifted block's
+    // bias / mask table (5.3 MB at 16 window types x 4 heads of 144 x 144: more than one L2 holds; with every window type on every XCD the
+    // backward of the stage-0 Swin block took 940 us instead of 690).  Measured against the plain order: -3 ... -45 % per launch.
+    const int kl = (int)(blockIdx.x >> 3) / p.heads, k = kl * 8 + (int)(blockIdx.x & 7);
+    const int item = k * p.heads + (int)(blockIdx.x >> 3) - kl * p.heads;
+    if (k >= p.items / p.heads) return;
+    const int head = item % p.heads, w = (item / p.heads) % p.nW, b = item / (p.heads * p.nW);
+    float dsc = 0.f;
+    wattn_bwd_win<NPAD, false>(p, b, w, head, smem, rows, sL, sD, sInv, nullptr, nullptr, dsc);
+  } else {
+    // workgroup g: destination d = g % (nwm * heads) -- (window type t, head h) -- and group g / (nwm * heads) of its R instances; with
+    // nwm * heads a multiple of 8 a destination (its bias table rows and its slab flush) stays on one XCD
+    extern __shared__ __attribute__((aligned(16))) float slab_dyn[];
+    __shared__ float sR[NPAD];                               // r_i = sum_j dS_ij of the current instance (pass 1 -> pass 2)
+    const int tid = threadIdx.x, lane = tid & 63, nd = p.nwm * p.heads;
+    const int d = (int)blockIdx.x % nd, grp = (int)blockIdx.x / nd, head = d % p.heads, t = d / p.heads;
+    const int n = p.n, nn = n * n;
+    float* slab = p.tab.dbm ? slab_dyn : nullptr;
+    if (slab)
+      for (int e = tid; e < nn; e += blockDim.x) slab[e] = 0.f;          // (ordered before the first use by the instance's first barrier)
+    float dsc = 0.f;
+    const int r0 = grp * p.tab.G, r1 = min(r0 + p.tab.G, p.tab.R);
+    for (int r = r0; r < r1; ++r) {
+      const int w = t + p.nwm * (r % p.tab.nper), b = r / p.tab.nper;
+      wattn_bwd_win<NPAD, true>(p, b, w, head, smem, rows, sL, sD, sInv, sR, slab, dsc);
+      __syncthreads();                                       // the next instance overwrites rows / images; the flush reads the slab
+    }
+    if (slab) {                                              // 64 consecutive floats per wave-instruction: 256 contiguous bytes per atomic
+      float* dst = p.tab.dbm + (long)d * nn;
+      for (int e = tid; e < nn; e += blockDim.x) unsafeAtomicAdd(dst + e, slab[e]);
+    }
+    if (p.tab.dscale) {
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) dsc += __shfl_xor(dsc, o, 64);
+      if (lane == 0) unsafeAtomicAdd(p.tab.dscale + head, dsc);
+    }
   }
 }
 }  // namespace
@@ -414,9 +494,66 @@ int window_attn_backward(void* stream, int B, int H, int W, int ws, int shift, i
   const int nt = (a.n + 31) / 32, nw = nt;        // one wavefront per 32-row tile (n <= 144: <= 5; four waves left one with two of the five tiles)
   a.items = B * a.nW * heads; a.chunk = (B * a.nW + 7) / 8 * heads;
   const dim3 grid((unsigned)(8 * a.chunk));
-  if (a.n <= 64) hipLaunchKernelGGL(wattn_bwd_k<64>, grid, dim3(64 * nw), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(wattn_bwd_k<WMAXN>, grid, dim3(64 * nw), 0, (hipStream_t)stream, a);
+  if (a.n <= 64) hipLaunchKernelGGL((wattn_bwd_k<64, false>), grid, dim3(64 * nw), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((wattn_bwd_k<WMAXN, false>), grid, dim3(64 * nw), 0, (hipStream_t)stream, a);
+  return 0;
+}
+
+// Backward of trainable blocks: dqkv exactly as window_attn_backward (the same instructions per window instance), plus dbm / dscale
+// (either may be NULL), zeroed here on `stream` and summed by the table variant of the kernel.  Only libdgsct.so carries it (the host
+// emulation of the CPU tests has no counterpart: the C-ABI entry below lives in this file, not in capi.cpp).
+static int window_attn_backward_tables(void* stream, int B, int H, int W, int ws, int shift, int heads, int hd, int nwm, const void* qkv,
+                                       const float* bm, const float* scale, const void* out, const float* lse, const void* dout, void* dqkv,
+                                       float* dbm, float* dscale, int cosine) {
+  if (!wattn_check(B, H, W, ws, shift, heads, hd, nwm)) return 2;
+  WArgsT a{};
+  static_cast<WArgs&>(a) = wattn_args(B, H, W, ws, shift, heads, hd, nwm);
+  a.cosine = cosine;
+  a.qkv = (const unsigned short*)qkv; a.bm = bm; a.scale = scale; a.o_in = (const unsigned short*)out; a.lse = const_cast<float*>(lse);
+  a.dout = (const unsigned short*)dout; a.dqkv = (unsigned short*)dqkv;
+  a.tab.dbm = dbm; a.tab.dscale = dscale;
+  const int nn = a.n * a.n, D = nwm * heads;
+  a.tab.nper = a.nW / nwm;
+  a.tab.R = B * a.tab.nper;                                  // window instances per destination (window type, head)
+  // G instances per workgroup: deep enough that the slab flush is small next to the backward (G >= 8: <= 1/8 of per-instance flushes), as
+  // shallow as keeps two rounds of workgroups on every CU (resident per CU: 4 at <= 64 tokens -- 21 KB + a 16 KB slab --, 1 at 144 -- 53 +
+  // 81 KB); a batch too small for both fills the 256 CUs first
+  const long inst = (long)D * a.tab.R, target = 2L * 256 * (a.n <= 64 ? 4 : 1);
+  int G = (int)std::max(8L, (inst + target - 1) / target);
+  if (inst / G < 256) G = (int)std::max(1L, inst / 256);
+  G = std::min(G, a.tab.R);
+  a.tab.G = G;
+  const int groups = (a.tab.R + G - 1) / G;
+  hipStream_t st = (hipStream_t)stream;
+  if (dbm && hipMemsetAsync(dbm, 0, sizeof(float) * (size_t)nwm * heads * nn, st) != hipSuccess) { set_error("window attention: zeroing dbm failed"); return 1; }
+  if (dscale && hipMemsetAsync(dscale, 0, sizeof(float) * (size_t)heads, st) != hipSuccess) { set_error("window attention: zeroing dscale failed"); return 1; }
+  const int nt = (a.n + 31) / 32;
+  const dim3 grid((unsigned)(D * groups)), block((unsigned)(64 * nt));
+  const size_t shmem = dbm ? sizeof(float) * (size_t)nn : 0;
+  if (a.n <= 64) {
+    hipLaunchKernelGGL((wattn_bwd_k<64, true>), grid, block, shmem, st, a);
+  } else {
+    auto kern = wattn_bwd_k<WMAXN, true>;
+    if (shmem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL(kern, grid, block, shmem, st, a);
+  }
   return 0;
 }
 
 }  // namespace dgsct
+
+// C-ABI entry (include/dgsct.h).  Defined here rather than in capi.cpp so that the host emulation library, which links capi.cpp against
+// host loops, needs no counterpart; callers bind it optionally (dg-sct_amd/_lib.py: Lib.has_window_attn_tables).
+extern "C" int dgsct_window_attn_backward_tables(int B, int H, int W, int ws, int shift, int heads, int hd, int nwm, int flags, const void* qkv,
+                                                 const float* bm, const float* scale, const void* out, const float* lse, const void* dout,
+                                                 void* dqkv, float* dbm, float* dscale, void* stream) {
+  dgsct::clear_error();
+  dgsct::clear_async();
+  if (!qkv || !bm || !scale || !out || !lse || !dout || !dqkv) { dgsct::set_error("dgsct_window_attn_backward_tables: NULL argument"); return 2; }
+  if (flags & ~DGSCT_WATTN_COSINE) { dgsct::set_error("dgsct_window_attn_backward_tables: unknown flag bits 0x%x", flags); return 2; }
+  const int rc = dgsct::window_attn_backward_tables(stream, B, H, W, ws, shift, heads, hd, nwm, qkv, bm, scale, out, lse, dout, dqkv, dbm,
+                                                    dscale, flags & DGSCT_WATTN_COSINE);
+  if (rc) return rc;
+  dgsct::check_async("dgsct_window_attn_backward_tables");
+  return dgsct::has_error() ? 1 : 0;
+}

@@ -7,6 +7,7 @@ import contextlib
 import dataclasses
 import os
 import threading
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -676,7 +677,8 @@ def map_pool(f: torch.Tensor, spatial_att_maps: torch.Tensor, lib: Optional[Lib]
 # ---- fused window attention of the frozen backbone blocks -------------------------------------------------------
 class _WindowAttnFn(torch.autograd.Function):
     """softmax(scale q k^T + bm) v per (frame, window, head) on the qkv projection of the UN-partitioned map; window partition and cyclic
-    shift are address arithmetic inside the kernel (csrc/wattn.hip).  bm / scale are frozen tables: no gradient."""
+    shift are address arithmetic inside the kernel (csrc/wattn.hip).  When autograd asks for the gradient of bm or scale (trainable blocks)
+    the backward is the table variant (dgsct_window_attn_backward_tables: the same dqkv, plus dbm / dscale); otherwise the frozen one."""
 
     @staticmethod
     def forward(ctx, lib, qkv, bm, scale, H, W, ws, shift, heads, cosine=False):
@@ -701,11 +703,35 @@ class _WindowAttnFn(torch.autograd.Function):
         if dout.dtype != qkv.dtype:
             dout = dout.to(qkv.dtype)
         dqkv = torch.empty_like(qkv)
+        want_bm, want_scale = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if (want_bm or want_scale) and not ctx.lib.has_window_attn_tables:
+            _warn_no_tables(ctx.lib)
+            want_bm = want_scale = False
         _mark_stream_use(qkv, bm, scale, out, lse, dout)
+        dbm = dscale = None
         with _dev_guard(qkv):
-            ctx.lib.window_attn_backward(ctx.geom, qkv.data_ptr(), bm.data_ptr(), scale.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                         dout.data_ptr(), dqkv.data_ptr(), _stream_of(qkv), ctx.flags)
-        return None, dqkv, None, None, None, None, None, None, None, None
+            if want_bm or want_scale:
+                dbm = torch.empty_like(bm) if want_bm else None                      # (zeroed by the call)
+                dscale = torch.empty_like(scale) if want_scale else None
+                ctx.lib.window_attn_backward_tables(ctx.geom, qkv.data_ptr(), bm.data_ptr(), scale.data_ptr(), out.data_ptr(),
+                                                    lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(),
+                                                    dbm.data_ptr() if dbm is not None else None,
+                                                    dscale.data_ptr() if dscale is not None else None, _stream_of(qkv), ctx.flags)
+            else:
+                ctx.lib.window_attn_backward(ctx.geom, qkv.data_ptr(), bm.data_ptr(), scale.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                             dout.data_ptr(), dqkv.data_ptr(), _stream_of(qkv), ctx.flags)
+        return None, dqkv, dbm, dscale, None, None, None, None, None, None
+
+
+_WARNED_NO_TABLES = set()
+
+
+def _warn_no_tables(lib):
+    """a library without dgsct_window_attn_backward_tables (the host emulation): the tables get no gradient, as before it existed"""
+    if lib.path not in _WARNED_NO_TABLES:
+        _WARNED_NO_TABLES.add(lib.path)
+        warnings.warn(f"dg-sct_amd: {lib.path} has no dgsct_window_attn_backward_tables: the window-attention bias / scale tables get no "
+                      f"gradient through it", RuntimeWarning, stacklevel=3)
 
 
 def window_attention_supported(qkv: torch.Tensor, ws: int, heads: int) -> bool:
@@ -723,8 +749,13 @@ def window_attention(qkv: torch.Tensor, bm: torch.Tensor, scale: torch.Tensor, H
     cosine: q and k are L2-normalised per head inside the kernel (Swin-V2), qkv is the raw projection."""
     if not window_attention_supported(qkv, ws, heads):
         raise RuntimeError("dg-sct_amd: window_attention takes bf16 qkv with head width 8/16/24/32 and windows of <= 144 tokens")
-    if bm.dtype != torch.float32 or scale.dtype != torch.float32 or bm.shape[1:] != (heads, ws * ws, ws * ws):
-        raise RuntimeError("dg-sct_amd: window_attention: bm must be fp32 [1 | windows, heads, n, n] and scale fp32 [heads]")
+    nW = (H // ws) * (W // ws) if ws > 0 else 0
+    if qkv.shape[1] != H * W:
+        raise RuntimeError(f"dg-sct_amd: window_attention: qkv holds {qkv.shape[1]} tokens per frame, the map {H} x {W} = {H * W}")
+    if (bm.dtype != torch.float32 or scale.dtype != torch.float32 or bm.dim() != 4 or bm.shape[1:] != (heads, ws * ws, ws * ws)
+            or bm.shape[0] not in (1, nW) or tuple(scale.shape) != (heads,)):
+        raise RuntimeError(f"dg-sct_amd: window_attention: bm must be fp32 [1 | {nW}, {heads}, {ws * ws}, {ws * ws}] and scale fp32 [{heads}] "
+                           f"(got {tuple(bm.shape)} {bm.dtype}, {tuple(scale.shape)} {scale.dtype})")
     from ._lib import default_lib
     return _WindowAttnFn.apply(lib or default_lib(), qkv.contiguous(), bm.contiguous(), scale.contiguous(), H, W, ws, shift, heads, cosine)
 

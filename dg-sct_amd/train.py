@@ -3,7 +3,8 @@
 
 * ``trainable_by_name`` -- the freeze rule (``main_trans.py:211-256``): ``'ViT'``/``'swin'`` (optionally their norms) and
   ``'htsat'`` parameters are frozen; ``'adapter_blocks'``, ``'CMBS'``, ``'mlp_class'`` and ``'temporal_attn'`` train;
-  ``'mlp_class'`` gets its own learning rate (``:257-260``).
+  ``'mlp_class'`` gets its own learning rate (``:257-260``).  ``task="avs_s4"``: AVS-S4's rule (``avs_s4/train.py:145-163``) --
+  ``'ViT'``/``'swin'`` frozen, everything else (the HTS-AT blocks included) trains.
 * ``make_optimizer`` -- ``optim.Adam(param_group)`` + ``StepLR(step_size=decay_epoch, gamma=decay)`` (``:276-278``) with the
   values of ``AVE/train.sh`` (lr 5e-4, lr_mlp 5e-6, decay 0.35 every 3 epochs).
 * ``shard_clips`` / ``seed_everything`` -- per-rank sharding and seeding: the reference has one process (``--seed 43``,
@@ -29,12 +30,23 @@ import torch
 TRAIN_KEYS = ("adapter_blocks", "CMBS", "mlp_class", "temporal_attn")      # main_trans.py:242-256
 
 
+TASKS = ("ave", "avs_s4")
+
+
 def trainable_by_name(named_parameters: Iterable[Tuple[str, torch.nn.Parameter]], is_vit_ln: bool = False, lr: float = 5e-4,
-                      lr_mlp: float = 5e-6) -> List[Dict]:
+                      lr_mlp: float = 5e-6, task: str = "ave") -> List[Dict]:
     """Sets ``requires_grad`` by the reference's name rule and returns its ``param_group`` list (one entry per parameter,
-    like the reference; frozen parameters are listed too -- Adam skips tensors without gradients)."""
+    like the reference; frozen parameters are listed too -- Adam skips tensors without gradients).
+    task "ave": main_trans.py:211-256 (is_vit_ln: the 'ViT'/'swin' norms train too); "avs_s4": avs_s4/train.py:145-163 ('ViT'/'swin'
+    frozen, every other parameter trains; is_vit_ln does not apply)."""
+    if task not in TASKS:
+        raise ValueError(f"task must be one of {TASKS}, got {task!r}")
     groups = []
     for name, p in named_parameters:
+        if task == "avs_s4":
+            p.requires_grad = not ("ViT" in name or "swin" in name)
+            groups.append({"params": p, "lr": lr})                  # (one learning rate: avs_s4/train.py builds Adam on all parameters)
+            continue
         p.requires_grad = False
         if "ViT" in name or "swin" in name:
             p.requires_grad = bool(is_vit_ln) and "norm" in name
@@ -47,8 +59,8 @@ def trainable_by_name(named_parameters: Iterable[Tuple[str, torch.nn.Parameter]]
 
 
 def make_optimizer(model: torch.nn.Module, lr: float = 5e-4, lr_mlp: float = 5e-6, decay: float = 0.35, decay_epoch: int = 3,
-                   is_vit_ln: bool = False, fused: Optional[bool] = None):
-    groups = trainable_by_name(model.named_parameters(), is_vit_ln, lr, lr_mlp)
+                   is_vit_ln: bool = False, fused: Optional[bool] = None, task: str = "ave"):
+    groups = trainable_by_name(model.named_parameters(), is_vit_ln, lr, lr_mlp, task=task)
     kw = {}
     if fused is None:
         fused = all(g["params"].is_cuda for g in groups)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DGSCT_VERSION 100
+#define DGSCT_VERSION 101
 enum { DGSCT_F32 = 0, DGSCT_BF16 = 1,
        DGSCT_BF16_FP8 = 2 };  /* bf16 storage / MFMA everywhere, plus fp8 (OCP e4m3) MFMA operands for the three big weight-stationary
                                  forward projections fc, fc_affine_video_1, fc_affine_video_2 (BASELINE.json configs[4]); buffers are
@@ -205,14 +205,15 @@ int dgsct_map_pool_forward(int dtype, int BT, int N, int C, const void* F, const
 int dgsct_map_pool_backward(int dtype, int BT, int N, int C, const void* F, const float* map, const float* dPooled,
                             void* dF, float* dMap, void* stream);
 
-/* ---- fused window attention of the FROZEN backbone blocks ------------------------------------
+/* ---- fused window attention of the backbone blocks ------------------------------------------
  * Replaces the body of HTS-AT's `WindowAttention.forward` between its qkv and proj Linears (DG-SCT/AVE/nets/htsat.py:103-131)
  * together with the window partition / reverse and the cyclic `torch.roll`s of the block around it (htsat.py:196-229), and the same
  * part of the timm Swin-V2 block the AVE loop calls at DG-SCT/AVE/nets/net_trans.py:894 (cosine form: q, k passed in normalised):
  *   O[b][p(w,i)][h][:] = sum_j softmax_j( scale[h] * q_i . k_j + bm[w % nwm][h][i][j] ) v_j
  * qkv  : bf16 [B][H*W][3][heads][hd] -- the qkv projection of the UN-partitioned, un-rolled token-major map;
  * bm   : fp32 [nwm][heads][n][n], n = ws*ws -- relative-position bias plus (nwm = number of windows) the additive shift mask;
- *        nwm = 1 for un-shifted blocks.  Frozen: no gradient is produced for it or for `scale` (fp32 [heads]);
+ *        nwm = 1 for un-shifted blocks.  scale: fp32 [heads].  The two entries below treat bm and scale as constants (frozen blocks);
+ *        dgsct_window_attn_backward_tables also returns their gradients (trainable blocks);
  * out  : bf16 [B][H*W][heads][hd];   lse: fp32 [B][windows][heads][n] (kept for backward);
  * backward: dqkv laid out like qkv, every element written (no pre-zeroing needed).
  * p(w,i) is the map position of token i of window w after the block's roll by -shift: ((wy*ws + iy + shift) % H, (wx*ws + ix + shift) % W).
@@ -229,6 +230,16 @@ int dgsct_window_attn_forward_ex(int B, int H, int W, int ws, int shift, int hea
                                  const float* scale, void* out, float* lse, void* stream);
 int dgsct_window_attn_backward_ex(int B, int H, int W, int ws, int shift, int heads, int hd, int nwm, int flags, const void* qkv, const float* bm,
                                   const float* scale, const void* out, const float* lse, const void* dout, void* dqkv, void* stream);
+/* Backward of a TRAINABLE block (since DGSCT_VERSION 101): dqkv exactly as dgsct_window_attn_backward_ex computes it (bit for bit), plus
+ *   dbm[t][h][i][j] = sum over frames b and windows w with w % nwm == t of dS_{b,w,h}[i][j]     fp32 [nwm][heads][n][n], the shape of bm
+ *   dscale[h]       = sum over b, w, i, j of dS_{b,w,h}[i][j] * (q_i . k_j)                     fp32 [heads]
+ * where dS = P o (dP - rowsum(dP o P)) is the gradient of the logits and q, k are the rows the logits were formed from (normalised under
+ * DGSCT_WATTN_COSINE).  Either of dbm / dscale may be NULL (not wanted).  The call zeroes both itself, on `stream`, before it adds into
+ * them (fp32 float atomics: the last bits may differ from run to run).  Optional export: a library built without it (the host emulation
+ * of the CPU tests) leaves it undefined, so bind it by name and fall back to the frozen entry. */
+int dgsct_window_attn_backward_tables(int B, int H, int W, int ws, int shift, int heads, int hd, int nwm, int flags, const void* qkv,
+                                      const float* bm, const float* scale, const void* out, const float* lse, const void* dout, void* dqkv,
+                                      float* dbm, float* dscale, void* stream);
 
 /* ---- LayerNorm (+ residual) of the FROZEN backbone blocks ------------------------------------
  * Replaces `self.norm1(x)` / `self.norm2(x)` of the HTS-AT block (DG-SCT/AVE/nets/htsat.py:192, :236) and, with `residual`, the whole
