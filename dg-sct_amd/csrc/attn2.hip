@@ -15,7 +15,6 @@
 //   TF [C/32][2][2][32][8]     : element (((j*2 + kk)*2 + h)*32 + c)*8 + e    = hi of tok[16 kk + 4 h + (e&3) + 8 (e>>2)][32 j + c]
 // (TF's latent-token order is the order in which a lane holds the probabilities of its token row after the first product).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
@@ -293,10 +292,7 @@ __global__ __launch_bounds__(256) void xattn_fwd2_k(const XF2Args p) {
     slab_copy_out(img, Og, nullptr, C, rows, c0, p.C, lane);
   }
 }
-bool attn2_ok(const Ctx& ctx, int C) {
-  static const bool v1 = getenv("DGSCT_ATTN_V1") != nullptr;
-  return ctx.mode == DT_BF16 && C % 32 == 0 && !v1;
-}
+bool attn2_ok(const Ctx& ctx, int C) { return ctx.mode == DT_BF16 && C % 32 == 0; }
 void xattn_fwd2(const Ctx& ctx, const void* X, const void* tokpk, const float* gate_av, int B, int N, int C, int tk, void* X1) {
   const int nrb = (N + 31) / 32;
   XF2Args a{(const unsigned short*)X, (const unsigned short*)tokpk, gate_av, N, C, tk, nrb, B * nrb, (unsigned short*)X1};
@@ -481,8 +477,7 @@ void xattn_bwd2(const Ctx& ctx, const void* X, const void* dX1, const void* tokp
   XB2Args a{(const unsigned short*)X, (const unsigned short*)dX1, (const unsigned short*)tokpk, gate_av, N, C, tk, wpf,
             (unsigned short*)dX, (const unsigned short*)R2, dtok, dgate};
   if (xattn_bwd3_launch(ctx, a, B)) return;
-  static const bool nokeep = getenv("DGSCT_ATTN_NOKEEPX") != nullptr;
-  if (C <= CS2 && !nokeep) hipLaunchKernelGGL(xattn_bwd2_k<true>, dim3(B * wpf), dim3(256), 0, (hipStream_t)ctx.stream, a);
+  if (C <= CS2) hipLaunchKernelGGL(xattn_bwd2_k<true>, dim3(B * wpf), dim3(256), 0, (hipStream_t)ctx.stream, a);
   else hipLaunchKernelGGL(xattn_bwd2_k<false>, dim3(B * wpf), dim3(256), 0, (hipStream_t)ctx.stream, a);
 }
 
@@ -956,192 +951,22 @@ bool tokattn_bwd_csplit(int B, int N, int C) {
 
 // ====================================================================================================================
 // tokattn_fwd for short frames (N <= 256: the stage-2/3 shapes, 32 of the 48 adapter calls of the AVE stack): ONE workgroup
-// per frame produces the final tok (fp32 + packed bf16 images), lse, a and aE -- no partial results, no combine launch, no
-// pack launch.  Phase A: the 4 waves split the frame's 32-row tiles and compute logits^T[n][t] = Yp[n] . T0[t] (Yp rows
-// from the private image as the A operand, packed my_tokens from global as B), so the softmax axis n runs along the
-// accumulator registers; the probabilities go to ONE shared LDS image [n][t].  Phase B: the waves split the 128-channel
-// slabs instead and walk ALL row tiles: O[t][c] = sum_n P[n][t] Yp[n][c] with both operands transpose-read.
+// of EIGHT wavefronts per frame produces the final tok (fp32 + packed bf16 images), lse, a and aE -- no partial results, no
+// combine launch, no pack launch.
+//   phase A: logits^T[n][t] = Yp[n] . T0[t] (Yp rows from the wave's private image as the A operand, packed my_tokens from
+//            global as B), so the softmax axis n runs along the accumulator registers; one 32-row tile per wave (N <= 256 = 8
+//            tiles); when the frame has <= 4 row tiles the spare waves split the 128-channel SLABS of a tile (partial logit
+//            tiles summed through LDS).  The probabilities go to ONE shared LDS image [n][t];
+//   phase B: the waves split the channels instead, in items of 64 (C / 64 = 6 ... 16 items over 8 waves: two MFMA column
+//            tiles per item), and walk ALL row tiles: O[t][c] = sum_n P[n][t] Yp[n][c] with both operands transpose-read.
+// (At one wave per SIMD -- the first version, four waves, two row tiles x every slab per wave in phase A and one 128-channel
+//  slab x every row tile in phase B -- the kernel was a latency chain on 160 of 256 CUs.)  N = 144, C = 512 alone: see
+// profiles/r06_attn_bench.txt.
 // ====================================================================================================================
 struct TFS2Args {
   const unsigned short* Yp; const float* T0; const unsigned short* T0pk; int N, C, tk; float invN;
   float* tok; unsigned short* tokpk; float* lse; float* a; unsigned short* aE;
 };
-__global__ __launch_bounds__(256) void tokattn_fwd_small_k(const TFS2Args p) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * IMG2 + 256 * PP2];
-  __shared__ float red[2][4][32];
-  __shared__ float sl[32];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x;
-  const long C = p.C;
-  char* img = smem + wave * IMG2;
-  char* sP = smem + 4 * IMG2;
-  const unsigned short* Yb = p.Yp + (long)b * p.N * C;
-  const unsigned short* thF = p.T0pk;
-  const unsigned short* tlF = thF + 32 * C;
-  const int nrt = (p.N + 31) / 32, nsl = (p.C + CS2 - 1) / CS2;
-  const int t = lane & 31;
-  // ---- phase A
-  f32x16 acc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int rt = wave + 4 * i;
-    if (rt >= nrt) break;
-    const int rows = p.N - rt * 32 < 32 ? p.N - rt * 32 : 32;
-    const unsigned short* Yg = Yb + (long)rt * 32 * C;
-    Slab s;
-    slab_load(s, Yg, C, rows, 0, p.C, lane);
-    for (int si = 0; si < nsl; ++si) {
-      const int c0 = si * CS2, kc = (p.C - c0 < CS2 ? p.C - c0 : CS2) / 16;
-      wave_sync();
-      slab_store_lds(s, img, rows, c0, p.C, lane);
-      wave_sync();
-      if (si + 1 < nsl) slab_load(s, Yg, C, rows, c0 + CS2, p.C, lane);
-      const unsigned short* bh = thF + ((long)(c0 >> 4) * 64 + lane) * 8;
-      const unsigned short* bl = tlF + ((long)(c0 >> 4) * 64 + lane) * 8;
-      const char* ap = img + (lane & 31) * PX2 + (lane >> 5) * 16;
-#pragma unroll
-      for (int g = 0; g < CS2 / 64; ++g) {
-        if (g * 4 >= kc) break;
-        bfx8 fh[4], fl[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int kk = g * 4 + q < kc ? g * 4 + q : 0; fh[q] = ldg8(bh + kk * 512); fl[q] = ldg8(bl + kk * 512); }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (g * 4 + q < kc) {
-            const bfx8 af = lds8(ap + (g * 4 + q) * 32);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, fh[q], acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, fl[q], acc[i], 0, 0, 0);
-          }
-      }
-    }
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if ((wave + 4 * i) * 32 + mt_row(r, lane) < p.N) mx = fmaxf(mx, acc[i][r]);
-  mx = fmaxf(mx, xor32b(mx));
-  if (lane < 32) red[0][wave][t] = mx;
-  __syncthreads();
-  const float m = fmaxf(fmaxf(red[0][0][t], red[0][1][t]), fmaxf(red[0][2][t], red[0][3][t]));
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int rt = wave + 4 * i;
-    if (rt >= nrt) break;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int n = rt * 32 + mt_row(r, lane);
-      const float pv = n < p.N ? __expf(acc[i][r] - m) : 0.f;
-      sum += pv;
-      *reinterpret_cast<unsigned short*>(sP + n * PP2 + t * 2) = f2bf(pv);
-    }
-  }
-  sum += xor32b(sum);
-  if (lane < 32) red[1][wave][t] = sum;
-  __syncthreads();
-  if (wave == 0 && lane < 32) {
-    const float l = red[1][0][t] + red[1][1][t] + red[1][2][t] + red[1][3][t];
-    sl[t] = 1.f / l;
-    if (t < p.tk) p.lse[(long)b * p.tk + t] = m + __logf(l);
-  }
-  __syncthreads();
-  // ---- phase B: wave -> slabs wave, wave + 4, ...
-  unsigned short* hiF = p.tokpk + (long)b * 96 * C;
-  unsigned short* loF = hiF + 32 * C;
-  unsigned short* TFo = loF + 32 * C;
-  for (int si = wave; si < nsl; si += 4) {
-    const int c0 = si * CS2, nt = (p.C - c0 < CS2 ? p.C - c0 : CS2) / 32;
-    f32x16 o[CS2 / 32];
-#pragma unroll
-    for (int j = 0; j < CS2 / 32; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
-    float cs0 = 0.f, cs1 = 0.f;                                   // column sums of channels c0 + 2 lane, + 1
-    Slab s;
-    slab_load(s, Yb, C, p.N < 32 ? p.N : 32, c0, p.C, lane);
-    // my_tokens of this slab for the epilogue, requested NOW: they do not depend on O, and 16 L2 round trips per tile in front of each
-    // tile's stores were the largest part of the kernel on wide frames (23 of 47 us at N = 36, C = 1024: eight tiles per wave)
-    float t0s[CS2 / 32][16];
-#pragma unroll
-    for (int j = 0; j < CS2 / 32; ++j) {
-      const int c = c0 + 32 * j + (lane & 31), cj = c < p.C ? c : 0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { const int tt = mt_row(r, lane); t0s[j][r] = p.T0[(long)(tt < p.tk ? tt : 0) * C + cj]; }
-    }
-    for (int rt = 0; rt < nrt; ++rt) {
-      const int rows = p.N - rt * 32 < 32 ? p.N - rt * 32 : 32;
-      wave_sync();
-      slab_store_lds(s, img, rows, c0, p.C, lane);
-      wave_sync();
-      if (rt + 1 < nrt) slab_load(s, Yb + (long)(rt + 1) * 32 * C, C, p.N - (rt + 1) * 32 < 32 ? p.N - (rt + 1) * 32 : 32, c0, p.C, lane);
-      const mt_bf16x8 a0 = mt_frag_mn(sP + rt * 32 * PP2, PP2, 0, 0, lane), a1 = mt_frag_mn(sP + rt * 32 * PP2, PP2, 0, 1, lane);
-#pragma unroll
-      for (int j = 0; j < CS2 / 32; ++j) {
-        if (j >= nt) break;
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, mt_frag_mn(img, PX2, 32 * j, 0, lane), o[j], 0, 0, 0);
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, mt_frag_mn(img, PX2, 32 * j, 1, lane), o[j], 0, 0, 0);
-      }
-#pragma unroll 8
-      for (int r = 0; r < 32; ++r) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(img + r * PX2 + lane * 4);
-        cs0 += __uint_as_float(w << 16); cs1 += __uint_as_float(w & 0xffff0000u);
-      }
-    }
-    if (c0 + 2 * lane < p.C) {
-      const float a0v = cs0 * p.invN, a1v = cs1 * p.invN;
-      *reinterpret_cast<float2*>(p.a + (long)b * C + c0 + 2 * lane) = make_float2(a0v, a1v);
-      *reinterpret_cast<unsigned*>(p.aE + (long)b * C + c0 + 2 * lane) = pack2(a0v, a1v);
-    }
-    // epilogue: tok = T0 + O / l; fp32 rows + the three packed bf16 images
-#pragma unroll
-    for (int j = 0; j < CS2 / 32; ++j) {
-      if (j >= nt) break;
-      const int c = c0 + 32 * j + (lane & 31);
-      float v[16];
-      // (T0 was loaded unconditionally from clamped rows above: `tt < tk ? T0[..] : 0` compiles to branch + load + s_waitcnt vmcnt(0)
-      //  PER ELEMENT -- the hipcc pitfall of gemm.hip's guarded staging)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int tt = mt_row(r, lane);
-        v[r] = tt < p.tk ? t0s[j][r] + o[j][r] * sl[tt] : 0.f;
-        if (tt < p.tk) p.tok[((long)b * p.tk + tt) * C + c] = v[r];
-        const unsigned short h = f2bf(v[r]);
-        // hi / lo of tok[tt][c] -> [tt][32 channels] images in the wave's (now free) slab image; whole 16-byte fragment
-        // pieces leave below (2-byte scattered global stores, 32 per lane and tile, were ~10 us of this kernel)
-        *reinterpret_cast<unsigned short*>(img + tt * 80 + (lane & 31) * 2) = h;
-        *reinterpret_cast<unsigned short*>(img + 2560 + tt * 80 + (lane & 31) * 2) = f2bf(v[r] - bf2f(h));
-      }
-      wave_sync();
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int q = lane + 64 * i, tt = q & 31, h8 = q >> 5;             // piece: token tt, channels 8 h8 .. + 7 of this tile
-        const int cc = c0 + 32 * j + 8 * h8;
-        const long fo = (((long)(cc >> 4) * 2 + ((cc >> 3) & 1)) * 32 + tt) * 8;
-        *reinterpret_cast<uint4*>(hiF + fo) = *reinterpret_cast<const uint4*>(img + tt * 80 + h8 * 16);
-        *reinterpret_cast<uint4*>(loF + fo) = *reinterpret_cast<const uint4*>(img + 2560 + tt * 80 + h8 * 16);
-      }
-      wave_sync();
-      // TF pieces (tile j of this slab, kk = 0 / 1, lane): the lane's registers [8 kk, 8 kk + 8) ARE the piece
-      unsigned short* tf = TFo + (((long)((c0 >> 5) + j) * 2) * 64 + lane) * 8;
-      *reinterpret_cast<uint4*>(tf) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-      *reinterpret_cast<uint4*>(tf + 512) = make_uint4(pack2(v[8], v[9]), pack2(v[10], v[11]), pack2(v[12], v[13]), pack2(v[14], v[15]));
-    }
-  }
-}
-
-// ---- round 6: the same kernel on EIGHT wavefronts (512 threads), same arithmetic and rounding points ------------------------------
-// The 4-wave kernel above is a latency chain at one wave per SIMD (160 workgroups on 256 CUs): phase A gives a wave up to two row
-// tiles x every 128-channel slab in turn (8 load -> LDS -> MFMA steps), phase B one slab x every row tile.  Here
-//   phase A: one row tile per wave (N <= 256 = 8 tiles); when the frame has <= 4 row tiles the spare waves split the SLABS of a tile
-//            (partial logit tiles summed through LDS: fp32 summation order differs from the 4-wave kernel, nothing else);
-//   phase B: items of 64 channels (C / 64 = 6 ... 16 items over 8 waves) instead of 128: two MFMA column tiles per item.
-// N = 144, C = 512 alone: see profiles/r06_attn_bench.txt.
 template <int HS>
 struct HSlab { uint4 v[HS / 16]; };
 template <int HS>
@@ -1286,6 +1111,8 @@ __global__ __launch_bounds__(TF8_NW * 64) void tokattn_fwd_small8_k(const TFS2Ar
     float cs0 = 0.f, cs1 = 0.f;                                   // column sums of channels c0 + 2 lane, + 1 (lanes 0 .. 31)
     HSlab<HS> s;
     hslab_load<HS>(s, Yb, C, p.N < 32 ? p.N : 32, c0, p.C, lane);
+    // my_tokens of this item for the epilogue, requested NOW: they do not depend on O, and 16 L2 round trips per tile in front of each
+    // tile's stores were the largest part of the kernel on wide frames
     float t0s[HS / 32][16];
 #pragma unroll
     for (int j = 0; j < HS / 32; ++j) {
@@ -1319,18 +1146,22 @@ __global__ __launch_bounds__(TF8_NW * 64) void tokattn_fwd_small8_k(const TFS2Ar
       *reinterpret_cast<float2*>(p.a + (long)b * C + c0 + 2 * lane) = make_float2(a0v, a1v);
       *reinterpret_cast<unsigned*>(p.aE + (long)b * C + c0 + 2 * lane) = pack2(a0v, a1v);
     }
-    // epilogue: tok = T0 + O / l; fp32 rows + the three packed bf16 images (as in the 4-wave kernel)
+    // epilogue: tok = T0 + O / l; fp32 rows + the three packed bf16 images
 #pragma unroll
     for (int j = 0; j < HS / 32; ++j) {
       if (j >= nt) break;
       const int c = c0 + 32 * j + (lane & 31);
       float v[16];
+      // (T0 was loaded unconditionally from clamped rows above: `tt < tk ? T0[..] : 0` compiles to branch + load + s_waitcnt vmcnt(0)
+      //  PER ELEMENT -- the hipcc pitfall of gemm.hip's guarded staging)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int tt = mt_row(r, lane);
         v[r] = tt < p.tk ? t0s[j][r] + o[j][r] * sl[tt] : 0.f;
         if (tt < p.tk) p.tok[((long)b * p.tk + tt) * C + c] = v[r];
         const unsigned short h = f2bf(v[r]);
+        // hi / lo of tok[tt][c] -> [tt][32 channels] images in the wave's (now free) slab image; whole 16-byte fragment
+        // pieces leave below (2-byte scattered global stores, 32 per lane and tile, were ~10 us of this kernel)
         *reinterpret_cast<unsigned short*>(img + tt * 80 + (lane & 31) * 2) = h;
         *reinterpret_cast<unsigned short*>(img + 2560 + tt * 80 + (lane & 31) * 2) = f2bf(v[r] - bf2f(h));
       }
@@ -1344,21 +1175,19 @@ __global__ __launch_bounds__(TF8_NW * 64) void tokattn_fwd_small8_k(const TFS2Ar
         *reinterpret_cast<uint4*>(loF + fo) = *reinterpret_cast<const uint4*>(img + 2560 + tt * 80 + h8 * 16);
       }
       wave_sync();
+      // TF pieces (tile j of this item, kk = 0 / 1, lane): the lane's registers [8 kk, 8 kk + 8) ARE the piece
       unsigned short* tf = TFo + (((long)((c0 >> 5) + j) * 2) * 64 + lane) * 8;
       *reinterpret_cast<uint4*>(tf) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
       *reinterpret_cast<uint4*>(tf + 512) = make_uint4(pack2(v[8], v[9]), pack2(v[10], v[11]), pack2(v[12], v[13]), pack2(v[14], v[15]));
     }
   }
 }
-static std::atomic<int> g_tfs8{1};
-int tokattn_small8_mode(int set) { const int old = g_tfs8.load(); if (set >= 0) g_tfs8.store(set); return old; }     // dgsct_test_tune "tfs8": 0 = the 4-wave kernel
 bool tokattn_fwd_small_ok(const Ctx& ctx, int N, int C) { return attn2_ok(ctx, C) && N <= 256; }
 void tokattn_fwd_small(const Ctx& ctx, const void* Yp, const float* T0, const void* T0pk, int B, int N, int C, int tk, float* tok,
                        void* tokpk, float* lse, float* a, void* aE) {
   TFS2Args q{(const unsigned short*)Yp, T0, (const unsigned short*)T0pk, N, C, tk, 1.f / (float)N, tok, (unsigned short*)tokpk, lse, a,
              (unsigned short*)aE};
-  if (g_tfs8.load(std::memory_order_relaxed)) hipLaunchKernelGGL(tokattn_fwd_small8_k, dim3(B), dim3(TF8_NW * 64), 0, (hipStream_t)ctx.stream, q);
-  else hipLaunchKernelGGL(tokattn_fwd_small_k, dim3(B), dim3(256), 0, (hipStream_t)ctx.stream, q);
+  hipLaunchKernelGGL(tokattn_fwd_small8_k, dim3(B), dim3(TF8_NW * 64), 0, (hipStream_t)ctx.stream, q);
 }
 
 }  // namespace dgsct

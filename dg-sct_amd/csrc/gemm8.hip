@@ -14,8 +14,8 @@
 //     v_mfma_f32_32x32x16_bf16 accumulators (96 / 128 VGPRs);
 //   * operands go global -> LDS by global_load_lds_dwordx4 (no staging registers, no ds_write pass) into TWO LDS
 //     buffers; the k-tile t+2 is requested as soon as every wave has finished reading tile t, so a tile's DMA has the
-//     whole MFMA phase of the tile in between to land: `s_waitcnt vmcnt(N)` with N = this wave's DMA instructions per
-//     k-tile (never 0 inside the loop), raw s_barrier (a __syncthreads would drain the DMA queue);
+//     whole MFMA phase of the tile in between to land; ONE raw s_barrier per k-tile, behind an `s_waitcnt vmcnt(0)` that
+//     finds only the next tile's DMA in flight (the k-loop in the kernel);
 //   * dense LDS images, conflict-free fragment reads by swizzling the SOURCE address of each 16-byte chunk:
 //     K-major tile [rows][64 k]: chunk c of row r at slot c ^ ((r >> 1) & 7), read with ds_read_b128;
 //     MN-major tile [64 k][rows]: chunk rc of k-row k at slot rc ^ swz_mn(k), read with ds_read_b64_tr_b16;
@@ -39,7 +39,8 @@ typedef __attribute__((ext_vector_type(8))) short g8_s16x8_t;
 typedef __attribute__((ext_vector_type(16))) float g8_f32x16_t;
 
 // Structure experiments of round 4 (compile-time, default = the round-3 kernel: 8 waves, 256-row tiles).  Timings of the remap
-// forward 2304 x (96 x 160) x 4096, K-major x MN-major, alone on the chip (tools/gemm_bench.py BIG=1, DGSCT_GEMM8_DBG switches):
+// forward 2304 x (96 x 160) x 4096, K-major x MN-major, alone on the chip (tools/gemm_bench.py BIG=1; the partial runs used debug
+// switches of the round-3 k-loop, since retired with it -- DESIGN_HISTORY.md):
 //                                             whole kernel   no DMA in the loop   DMA + barriers only   MFMAs + barriers only
 //   8 waves, 256 x 192 (64 x 96 per wave)        331 us           268 us               154 us                 196 us
 //   4 waves, 256 x 192 (128 x 96 per wave,
@@ -74,8 +75,8 @@ struct G8 {
   const float* r1_m; const float* r1_n; const float* bias_n;
   const char* R;                          // bf16 residual laid out like D (ldd, dbs), added in the row pass (plain stores only); NULL: none
   int gm;                                 // m-tiles per group of the work list (tile order, see the kernel)
-  int stag;                               // staggered DMA issue of the two wave halves (PIPE loop; dgsct_test_tune "g8stag")
-  int dbg;                                // DGSCT_GEMM8_DBG (timing experiments only, results are garbage): 1 no DMA in the loop, 2 no fragment reads, 4 no MFMA
+  int stag;                               // staggered DMA issue of the two wave halves (dgsct_test_tune "g8stag")
+  int dbg;                                // DGSCT_GEMM8_DBG (timing experiment, results unchanged): 16 = s_setprio 1 around every MFMA group
 };
 
 template <bool KM, int ROWS>
@@ -179,18 +180,11 @@ __device__ __forceinline__ g8_bf16x8_t g8_val(const G8F<false>& f) {
   g8_s16x8_t v = __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(g8_bf16x8_t, v);
 }
-// compiler-scheduled K-major fragment (both operands K-major: no transpose reads, hipcc's own lgkmcnt placement is good)
-template <int ROWS>
-__device__ __forceinline__ g8_bf16x8_t g8_frag_km(const char* lds, int row0, int kk, int lane) {
-  const int row = row0 + (lane & 31);
-  const int cc = kk * 2 + (lane >> 5);
-  return *reinterpret_cast<const g8_bf16x8_t*>(lds + row * 128 + ((cc ^ ((row >> 1) & 7)) * 16));
-}
 
 template <int N> __device__ __forceinline__ void g8_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// PIPE (round 5): the k-loop software-pipelined ACROSS k-tiles -- ONE barrier and no exposed LDS latency per k-tile (see the loop)
-template <bool AK, bool BK, int BN, bool BATCHED, bool TWO, bool PIPE>
+// The k-loop is software-pipelined ACROSS k-tiles -- ONE barrier and no exposed LDS latency per k-tile (see the loop)
+template <bool AK, bool BK, int BN, bool BATCHED, bool TWO>
 __global__ __launch_bounds__(G8_NT, (G8_NW == 8 || G8_ROWS == 128) ? 2 : 1)
 void gemm8_kernel(const G8 p) {
   constexpr int BM = G8_ROWS, WGN = 2, WGM = G8_NW / WGN, TM = BM / (WGM * 32), TN = BN / 64;
@@ -244,7 +238,6 @@ void gemm8_kernel(const G8 p) {
   };
   constexpr int NDMA = GA::NI + GB::NI;                      // DMA instructions per wave and k-tile
 
-  constexpr bool ASMRD = !(AK && BK);                        // any transpose-read operand: hand-ordered fragment reads
   const unsigned smem_lds = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
   // per-lane fragment addresses (buffer 0, k-step 0) of this wave's row blocks; K-major images add a k-step term kx[kk]
   unsigned baseA[TM], baseB[TN], kx[4];
@@ -255,182 +248,89 @@ void gemm8_kernel(const G8 p) {
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) kx[kk] = (unsigned)((((kk * 2 + (lane >> 5)) ^ (((lane & 31) >> 1) & 7)) * 16));
 
-  if constexpr (PIPE) {
-    // One k-tile = four 16-deep k-steps; fragment registers alternate between two sets.  Steady state of iteration `it` (tile `it` in
-    // buffer it & 1, its k-step 0 fragments already in set 0):
-    //     rd(1) | mma(0) | rd(2) | mma(1) | rd(3) | mma(2) | -- every read of tile `it` has returned --
-    //     s_waitcnt vmcnt(0) (this wave's pieces of tile it + 1: the only DMA group in flight) ; s_barrier
-    //         => tile it + 1 is visible to every wave AND every wave is done reading tile `it`: one barrier serves both hazards
-    //     DMA of tile it + 2 into buffer it & 1 ; rd(0) of tile it + 1 | mma(3)
-    // i.e. one barrier per k-tile instead of two, and the first fragment read of a tile flies under the last MFMA group of the tile
-    // before it instead of sitting exposed behind the barrier.
-    G8F<AK> fa[2][TM];
-    G8F<BK> fb[2][TN];
-    auto rdp = [&](auto kkc, unsigned boff) {
-      constexpr int KK = decltype(kkc)::value;
-      constexpr int S = KK & 1;
-      constexpr int PA = BM * 2, PB = BN * 2;
+  // One k-tile = four 16-deep k-steps; fragment registers alternate between two sets.  Steady state of iteration `it` (tile `it` in
+  // buffer it & 1, its k-step 0 fragments already in set 0):
+  //     rd(1) | mma(0) | rd(2) | mma(1) | rd(3) | mma(2) | -- every read of tile `it` has returned --
+  //     s_waitcnt vmcnt(0) (this wave's pieces of tile it + 1: the only DMA group in flight) ; s_barrier
+  //         => tile it + 1 is visible to every wave AND every wave is done reading tile `it`: one barrier serves both hazards
+  //     DMA of tile it + 2 into buffer it & 1 ; rd(0) of tile it + 1 | mma(3)
+  // i.e. one barrier per k-tile instead of two, and the first fragment read of a tile flies under the last MFMA group of the tile
+  // before it instead of sitting exposed behind the barrier.
+  G8F<AK> fa[2][TM];
+  G8F<BK> fb[2][TN];
+  auto rdp = [&](auto kkc, unsigned boff) {
+    constexpr int KK = decltype(kkc)::value;
+    constexpr int S = KK & 1;
+    constexpr int PA = BM * 2, PB = BN * 2;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if constexpr (AK) g8_rd128<0>(baseA[i] + boff + kx[KK], fa[S][i]);
-        else g8_rdtr<KK * 16 * PA, KK * 16 * PA + 4 * PA>(baseA[i] + boff, fa[S][i]);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (BK) g8_rd128<0>(baseB[j] + boff + kx[KK], fb[S][j]);
-        else g8_rdtr<KK * 16 * PB, KK * 16 * PB + 4 * PB>(baseB[j] + boff, fb[S][j]);
-      }
-    };
-    auto landedp = [&](int S) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < TM; ++i) g8_tie(fa[S][i]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) g8_tie(fb[S][j]);
-    };
-    const bool prio = p.dbg & 16;                              // experiment: s_setprio 1 around every MFMA group
-    auto mmap = [&](int S) {
-      if (prio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g8_val(fa[S][i]), g8_val(fb[S][j]), acc[i][j], 0, 0, 0);
-      if (prio) __builtin_amdgcn_s_setprio(0);
-    };
-    // (round 6, p.stag) The two waves of a SIMD are waves w and w + NW / 2.  In lock-step both issue their 7 LDS-DMA instructions of the
-    // tile after next right behind the barrier (~100 cycles each beside reads and MFMAs) while the SIMD's matrix pipe has nothing to do.
-    // With `stag` the upper half of the waves issues its share a quarter of a k-tile LATER (tile it + 1 into the buffer the barrier at
-    // the end of iteration it - 1 freed, behind the first MFMA group of iteration it; still covered by the vmcnt(0) in front of this
-    // iteration's barrier), so one wave of every SIMD multiplies while the other one issues.
-    const bool late = p.stag && wave >= G8_NW / 2;           // (half a k-tile later instead: measured, less -- the late half then waits for its own data)
-    if (nk > 0) {
-      issue(kt_begin, 0);
-      if (nk > 1) { issue(kt_begin + 1, 1); g8_wait_vm<NDMA>(); } else g8_wait_vm<0>();
-      __builtin_amdgcn_s_barrier();
-      rdp(std::integral_constant<int, 0>{}, 0u);
-      landedp(0);
-      for (int it = 0; it < nk; ++it) {
-        const unsigned boff = (unsigned)((it & 1) * STAGE), bnext = (unsigned)(((it + 1) & 1) * STAGE);
-        rdp(std::integral_constant<int, 1>{}, boff);
-        __builtin_amdgcn_sched_barrier(0);
-        mmap(0);
-        __builtin_amdgcn_sched_barrier(0);
-        landedp(1);
-        if (late && it >= 1 && it + 1 < nk) issue(kt_begin + it + 1, (it + 1) & 1);
-        rdp(std::integral_constant<int, 2>{}, boff);
-        __builtin_amdgcn_sched_barrier(0);
-        mmap(1);
-        __builtin_amdgcn_sched_barrier(0);
-        landedp(0);
-        rdp(std::integral_constant<int, 3>{}, boff);
-        __builtin_amdgcn_sched_barrier(0);
-        mmap(0);
-        __builtin_amdgcn_sched_barrier(0);
-        landedp(1);                                            // last read of tile `it` has returned
-        if (it + 1 < nk) {
-          g8_wait_vm<0>();                                     // tile it + 1 (the only group in flight) has landed
-          __builtin_amdgcn_s_barrier();
-          if (!late && it + 2 < nk) issue(kt_begin + it + 2, it & 1);
-          rdp(std::integral_constant<int, 0>{}, bnext);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mmap(1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (it + 1 < nk) landedp(0);
-      }
+    for (int i = 0; i < TM; ++i) {
+      if constexpr (AK) g8_rd128<0>(baseA[i] + boff + kx[KK], fa[S][i]);
+      else g8_rdtr<KK * 16 * PA, KK * 16 * PA + 4 * PA>(baseA[i] + boff, fa[S][i]);
     }
-  } else {
-  const bool dbg_nodma = p.dbg & 1, dbg_nord = p.dbg & 2, dbg_nomma = p.dbg & 4, dbg_early = p.dbg & 8;
-  if (nk > 0) issue(kt_begin, 0);
-  if (nk > 1) issue(kt_begin + 1, 1);
-  for (int it = 0; it < nk; ++it) {
-    // tile `it` has landed once this wave's older DMA group is done (the younger one, tile it+1, stays in flight) AND
-    // every other wave says the same of its part: wait, then barrier, then read
-    if (it + 1 < nk) g8_wait_vm<NDMA>(); else g8_wait_vm<0>();
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      if constexpr (BK) g8_rd128<0>(baseB[j] + boff + kx[KK], fb[S][j]);
+      else g8_rdtr<KK * 16 * PB, KK * 16 * PB + 4 * PB>(baseB[j] + boff, fb[S][j]);
+    }
+  };
+  auto landedp = [&](int S) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < TM; ++i) g8_tie(fa[S][i]);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) g8_tie(fb[S][j]);
+  };
+  const bool prio = p.dbg & 16;                              // experiment: s_setprio 1 around every MFMA group
+  auto mmap = [&](int S) {
+    if (prio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g8_val(fa[S][i]), g8_val(fb[S][j]), acc[i][j], 0, 0, 0);
+    if (prio) __builtin_amdgcn_s_setprio(0);
+  };
+  // (round 6, p.stag) The two waves of a SIMD are waves w and w + NW / 2.  In lock-step both issue their 7 LDS-DMA instructions of the
+  // tile after next right behind the barrier (~100 cycles each beside reads and MFMAs) while the SIMD's matrix pipe has nothing to do.
+  // With `stag` the upper half of the waves issues its share a quarter of a k-tile LATER (tile it + 1 into the buffer the barrier at
+  // the end of iteration it - 1 freed, behind the first MFMA group of iteration it; still covered by the vmcnt(0) in front of this
+  // iteration's barrier), so one wave of every SIMD multiplies while the other one issues.
+  const bool late = p.stag && wave >= G8_NW / 2;           // (half a k-tile later instead: measured, less -- the late half then waits for its own data)
+  if (nk > 0) {
+    issue(kt_begin, 0);
+    if (nk > 1) { issue(kt_begin + 1, 1); g8_wait_vm<NDMA>(); } else g8_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
-    if constexpr (!ASMRD) {
-      const char* la = smem + (it & 1) * STAGE;
-      const char* lb = la + GA::BYTES;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        g8_bf16x8_t af[TM], bf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = g8_frag_km<BM>(la, (wm * TM + i) * 32, kk, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = g8_frag_km<BN>(lb, (wn * TN + j) * 32, kk, lane);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+    rdp(std::integral_constant<int, 0>{}, 0u);
+    landedp(0);
+    for (int it = 0; it < nk; ++it) {
+      const unsigned boff = (unsigned)((it & 1) * STAGE), bnext = (unsigned)(((it + 1) & 1) * STAGE);
+      rdp(std::integral_constant<int, 1>{}, boff);
+      __builtin_amdgcn_sched_barrier(0);
+      mmap(0);
+      __builtin_amdgcn_sched_barrier(0);
+      landedp(1);
+      if (late && it >= 1 && it + 1 < nk) issue(kt_begin + it + 1, (it + 1) & 1);
+      rdp(std::integral_constant<int, 2>{}, boff);
+      __builtin_amdgcn_sched_barrier(0);
+      mmap(1);
+      __builtin_amdgcn_sched_barrier(0);
+      landedp(0);
+      rdp(std::integral_constant<int, 3>{}, boff);
+      __builtin_amdgcn_sched_barrier(0);
+      mmap(0);
+      __builtin_amdgcn_sched_barrier(0);
+      landedp(1);                                            // last read of tile `it` has returned
+      if (it + 1 < nk) {
+        g8_wait_vm<0>();                                     // tile it + 1 (the only group in flight) has landed
+        __builtin_amdgcn_s_barrier();
+        if (!late && it + 2 < nk) issue(kt_begin + it + 2, it & 1);
+        rdp(std::integral_constant<int, 0>{}, bnext);
       }
-      // every fragment read of this buffer has returned (the MFMAs consumed them); once all waves are here it may be refilled
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (it + 2 < nk && !dbg_nodma) issue(kt_begin + it + 2, it & 1);
-    } else {
-      const unsigned boff = (unsigned)((it & 1) * STAGE);
-      G8F<AK> fa[2][TM];
-      G8F<BK> fb[2][TN];
-      // k-step KK of this tile -> register set KK & 1
-      auto rd = [&](auto kkc) {
-        if (dbg_nord) return;
-        constexpr int KK = decltype(kkc)::value;
-        constexpr int S = KK & 1;
-        constexpr int PA = BM * 2, PB = BN * 2;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          if constexpr (AK) g8_rd128<0>(baseA[i] + boff + kx[KK], fa[S][i]);
-          else g8_rdtr<KK * 16 * PA, KK * 16 * PA + 4 * PA>(baseA[i] + boff, fa[S][i]);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          if constexpr (BK) g8_rd128<0>(baseB[j] + boff + kx[KK], fb[S][j]);
-          else g8_rdtr<KK * 16 * PB, KK * 16 * PB + 4 * PB>(baseB[j] + boff, fb[S][j]);
-        }
-      };
-      auto landed = [&](int S) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < TM; ++i) g8_tie(fa[S][i]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) g8_tie(fb[S][j]);
-      };
-      auto mma = [&](int S) {
-        if (dbg_nomma) return;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g8_val(fa[S][i]), g8_val(fb[S][j]), acc[i][j], 0, 0, 0);
-      };
-      // (sched_barrier on both sides of every MFMA group: left alone, hipcc hoists the NEXT group's lgkmcnt wait to just
-      //  behind the first MFMA, so the wave sat out the LDS latency with five MFMAs still to issue)
-      if (dbg_early && it + 2 < nk) issue(kt_begin + it + 2, it & 1);     // (timing experiment: overwrites the tile being read)
-      rd(std::integral_constant<int, 0>{});
-      landed(0);
-      rd(std::integral_constant<int, 1>{});                  // the reads of k-step 1 fly under the MFMAs of k-step 0
       __builtin_amdgcn_sched_barrier(0);
-      mma(0);
+      mmap(1);
       __builtin_amdgcn_sched_barrier(0);
-      landed(1);
-      rd(std::integral_constant<int, 2>{});
-      __builtin_amdgcn_sched_barrier(0);
-      mma(1);
-      __builtin_amdgcn_sched_barrier(0);
-      landed(0);
-      rd(std::integral_constant<int, 3>{});
-      __builtin_amdgcn_sched_barrier(0);
-      mma(0);
-      __builtin_amdgcn_sched_barrier(0);
-      landed(1);                                             // last read of this buffer has returned: it may be refilled
-      __builtin_amdgcn_s_barrier();
-      if (it + 2 < nk && !dbg_nodma && !dbg_early) issue(kt_begin + it + 2, it & 1);     // (address arithmetic + DMA issue interleave with the last MFMAs)
-      mma(1);
+      if (it + 1 < nk) landedp(0);
     }
-  }
-
   }
   // ---- epilogue.  accumulator element r of tile (i, j): row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), col = lane & 31
   const int ncol0 = n0 + wn * TN * 32;
@@ -511,31 +411,23 @@ void gemm8_kernel(const G8 p) {
 // k-loop); no caller of the adapter schedule has that shape -- gemm8_try leaves it to the tiled engine
 template <bool AK, bool BK, int BN> constexpr bool G8_TWO_OK = !(!AK && BK && BN == 256);
 
-template <bool AK, bool BK, int BN, bool PIPE>
+template <bool AK, bool BK, int BN>
 static void g8_launch_lay(const G8& k, bool batched, bool two, dim3 grid, hipStream_t s) {
-  if (batched)  hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, true, false, PIPE>), grid, dim3(G8_NT), 0, s, k);
+  if (batched)  hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, true, false>), grid, dim3(G8_NT), 0, s, k);
   else if (two) {
-    if constexpr (G8_TWO_OK<AK, BK, BN>) hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, false, true, PIPE>), grid, dim3(G8_NT), 0, s, k);
+    if constexpr (G8_TWO_OK<AK, BK, BN>) hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, false, true>), grid, dim3(G8_NT), 0, s, k);
   }
-  else          hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, false, false, PIPE>), grid, dim3(G8_NT), 0, s, k);
+  else          hipLaunchKernelGGL((gemm8_kernel<AK, BK, BN, false, false>), grid, dim3(G8_NT), 0, s, k);
 }
-template <int BN, bool PIPE>
-static void g8_launch_p(const G8& k, int ak, int bk, bool batched, bool two, dim3 grid, hipStream_t s) {
-  if (ak && bk)       g8_launch_lay<true, true, BN, PIPE>(k, batched, two, grid, s);
-  else if (ak && !bk) g8_launch_lay<true, false, BN, PIPE>(k, batched, two, grid, s);
-  else if (!ak && bk) g8_launch_lay<false, true, BN, PIPE>(k, batched, two, grid, s);
-  else                g8_launch_lay<false, false, BN, PIPE>(k, batched, two, grid, s);
-}
-// "g8pipe" (dgsct_test_tune / DGSCT_G8PIPE): 1 = the cross-tile pipelined k-loop (default), 0 = the round-3 loop (two barriers per k-tile)
-static std::atomic<int> g_g8pipe{getenv("DGSCT_G8PIPE") ? atoi(getenv("DGSCT_G8PIPE")) : 1};
-static std::atomic<int> g_g8stag{getenv("DGSCT_G8STAG") ? atoi(getenv("DGSCT_G8STAG")) : 1};      // 1: the upper wave half issues behind the first MFMA group of the next iteration (default), 0: lock-step
-int gemm8_stag_mode(int set) { const int old = g_g8stag.load(); if (set >= 0) g_g8stag.store(set ? 1 : 0); return old; }
-int gemm8_pipe_mode(int set) { const int old = g_g8pipe.load(); if (set >= 0) g_g8pipe.store(set ? 1 : 0); return old; }
 template <int BN>
 static void g8_launch(const G8& k, int ak, int bk, bool batched, bool two, dim3 grid, hipStream_t s) {
-  if (g_g8pipe.load(std::memory_order_relaxed)) g8_launch_p<BN, true>(k, ak, bk, batched, two, grid, s);
-  else g8_launch_p<BN, false>(k, ak, bk, batched, two, grid, s);
+  if (ak && bk)       g8_launch_lay<true, true, BN>(k, batched, two, grid, s);
+  else if (ak && !bk) g8_launch_lay<true, false, BN>(k, batched, two, grid, s);
+  else if (!ak && bk) g8_launch_lay<false, true, BN>(k, batched, two, grid, s);
+  else                g8_launch_lay<false, false, BN>(k, batched, two, grid, s);
 }
+static std::atomic<int> g_g8stag{getenv("DGSCT_G8STAG") ? atoi(getenv("DGSCT_G8STAG")) : 1};      // 1: the upper wave half issues behind the first MFMA group of the next iteration (default), 0: lock-step
+int gemm8_stag_mode(int set) { const int old = g_g8stag.load(); if (set >= 0) g_g8stag.store(set ? 1 : 0); return old; }
 
 static inline bool g8_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline double g8_eff(long wgs) { return (double)wgs / (double)(((wgs + 255) / 256) * 256); }
@@ -547,13 +439,12 @@ int gemm8_mode(int set) {
   return old;
 }
 
-// "g8wg" (dgsct_test_tune / DGSCT_G8WG; 0 = off): late-stage weight gradients (few 256 x 256 output tiles, a 23 040 .. 40 960-row
-// contraction) on this kernel with only as many split-K slabs as give ~`target` workgroups: a FEW CUs for longer instead of every CU
-// for a short burst that ends in 16-40-way atomics.  Round 4 measured the opposite choice (60 splits: 36.7 -> 61 us, kept off).  With
-// the aux join deferred (round 5) only the CU-time and the L2 traffic of these products count, not their latency: in-process A/B
-// (tools/call_overlap.py AB=g8wg=..): 32 -> -0.4 .. -0.7 ms per step, 64 -> -0.25, 96 -> +0.15, 16 -> noise.  Default 32.
-static std::atomic<int> g_g8wg{getenv("DGSCT_G8WG") ? atoi(getenv("DGSCT_G8WG")) : 32};
-int gemm8_wg_target(int set) { const int old = g_g8wg.load(); if (set >= 0) g_g8wg.store(set); return old; }
+// Late-stage weight gradients (few 256 x 256 output tiles, a 23 040 .. 40 960-row contraction) run on this kernel with only as many
+// split-K slabs as give ~G8_WG_TARGET workgroups: a FEW CUs for longer instead of every CU for a short burst that ends in 16-40-way
+// atomics.  Round 4 measured the opposite choice (60 splits: 36.7 -> 61 us, kept off).  With the aux join deferred (round 5) only the
+// CU-time and the L2 traffic of these products count, not their latency: in-process A/B of the target against the tiled engine:
+// 32 -> -0.4 .. -0.7 ms per step, 64 -> -0.25, 96 -> +0.15, 16 -> noise.
+constexpr int G8_WG_TARGET = 32;
 
 bool gemm8_try(const Ctx& ctx, const Gemm& g) {
   // DGSCT_GEMM8=0 switches the kernel off (A/B runs against the tiled engine); =2 also takes shapes below the size gates
@@ -617,9 +508,8 @@ bool gemm8_try(const Ctx& ctx, const Gemm& g) {
 
     // Few output tiles = many splits of a handful of k-tiles each: prologue / epilogue bound and 60-way atomics per address.
     // Measured (tools/gemm8_ab_all.sh): 512 x 512 x 23 040 36.7 -> 61 us, 1024 x 1024 x 5 760 35.9 -> 59 us -- the tiled engine keeps them.
-    const int wgt = g_g8wg.load(std::memory_order_relaxed);
-    if (wgt > 0 && tiles < 96 && !two && kt_total >= 48) {
-      splitk = (int)((wgt + tiles - 1) / tiles);
+    if (tiles < 96 && !two && kt_total >= 48) {
+      splitk = (int)((G8_WG_TARGET + tiles - 1) / tiles);
       if (splitk > kt_total / 8) splitk = kt_total / 8;
       if (splitk < 1) splitk = 1;
       goto split_done;
@@ -660,7 +550,7 @@ split_done:
   static const int gm_env = getenv("DGSCT_GEMM8_GM") ? atoi(getenv("DGSCT_GEMM8_GM")) : 4;
   k.gm = gm_env < 1 ? 1 : (gm_env > tiles_m ? tiles_m : gm_env);
   static const int dbg_env = getenv("DGSCT_GEMM8_DBG") ? atoi(getenv("DGSCT_GEMM8_DBG")) : 0;
-  k.dbg = dbg_env;
+  k.dbg = dbg_env & 16;
   k.stag = g_g8stag.load(std::memory_order_relaxed);
   dim3 grid((unsigned)tiles, splitk, 1);
   hipStream_t s = (hipStream_t)ctx.stream;

@@ -86,16 +86,6 @@ int plan_skip_mode(int set) { const int old = g_skip.load(); if (set >= 0) g_ski
 int plan_skip_minc(int set) { const int old = g_skip_minc.load(); if (set >= 0) g_skip_minc.store(set); return old; }
 int plan_skip_maxc(int set) { const int old = g_skip_maxc.load(); if (set >= 0) g_skip_maxc.store(set ? set : (1 << 30)); return old; }
 
-static bool wt_enabled() {
-  static const bool off = getenv("DGSCT_NO_WT") != nullptr;      // A/B switch: no transposed weight copies
-  return !off;
-}
-
-static bool vq1_dw_enabled() {
-  const char* e = getenv("DGSCT_VQ1_DW");
-  return e && atoi(e) != 0;
-}
-
 void Plan::layout() {
   // ---- prep: E copies of the GEMM weights (bf16 mode only) + derived fp32 vectors
   {
@@ -110,7 +100,7 @@ void Plan::layout() {
     // (2 workgroups per CU): 54.6 vs 32.9 us at 23040 x 512 x 512, and 26 vs 10 us for the M = 160 gate-MLP products
     auto wtcopy = [&](int id, int64_t cols) {
       wcols[id] = cols;
-      prep_wt[id] = (E == DT_BF16 && wt_enabled()) ? a.take("wt", wnumel[id] * es) : -1;
+      prep_wt[id] = (E == DT_BF16) ? a.take("wt", wnumel[id] * es) : -1;
     };
     wcopy(DGSCT_P_WN, (int64_t)N * No);
     wcopy(DGSCT_P_WC, (int64_t)C * Co);
@@ -242,10 +232,6 @@ void Plan::layout() {
     wb.rowpart = a.take("rowpart", row_part_floats(B, C) * 4);
     wb.rowpart_v1 = a.take("rowpart_v1", row_part_floats(B, C) * 4);   // partial sums whose second stage runs on the aux stream: not reused
     wb.rowpart_v2 = a.take("rowpart_v2", row_part_floats(B, C) * 4);
-    // per-workgroup dWv1 partials of vq1_bwd's experiment variant ("vq1fuse" = 3, slower, off by default): 19-34 MB that only that
-    // mode reads, so the region exists only when the process opted in (DGSCT_VQ1_DW=1, read per layout: tests set it around the call);
-    // without it "vq1fuse" = 3 behaves like 1
-    wb.vq1part = (vq1_fused_shape(E, N, C) && vq1_dw_enabled()) ? a.take("vq1part", vq1_wpart_floats(C) * 4) : -1;
     ws_bwd_bytes = a.off;
   }
   // ---- gradients (flat fp32)
@@ -602,8 +588,6 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
   // that only feeds parameter gradients -- also the three bias-side reductions that used to balance the tail of a joined call -- goes
   // to the aux stream
   const bool deferred = no_join && aux_stream;
-  static const bool bias_on_main = getenv("DGSCT_BIAS_ON_MAIN") && atoi(getenv("DGSCT_BIAS_ON_MAIN"));     // (A/B switch)
-  const bool bias_aux = deferred && !bias_on_main;
   auto dy_product = [&]() {
     Gemm g3;
     if (orderA) {
@@ -903,19 +887,14 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     }
   }
   // B5 ---- video query 1
-  bool vq1_in_kernel_dw = false, fx_x1 = false;
+  bool fx_x1 = false;
   {
     if (vq1_fused_supported(ctx.mode, N, C) && !fp8) {
       // the forward kept no vq1: ReLU decisions recomputed from X1, dvq1 (into vq1's region, for dWv1 below), d bias, dX1 += dvq1 . Wv1
       PartJob pj;
       Ctx cl = ctx; cl.late = aux_stream ? &pj : nullptr;
-      // "vq1fuse" = 3: dWv1 accumulated inside vq1_bwd (no dvq1 tensor, no product on the aux stream).  Measured (tools/call_overlap.py,
-      // AB=vq1fuse=3): the stage-0 pair's backward 3340 -> 3417 us -- C x C accumulators cost the pass its second workgroup per CU and
-      // the 32-deep contraction per block feeds the MFMAs badly; the aux-stream product it removes was overlapped anyway.  Off by default.
-      vq1_in_kernel_dw = wb.vq1part >= 0 && vq1fuse_mode(-1) == 3;
       vq1_bwd(cl, b.S(s.X1), b.W(DGSCT_P_WV1), b.F(DGSCT_P_BV1), b.Wk<float>(wb.coef), B, N, C, 1.f / (float)N, dX1, b.S(s.vq1),
-              G(DGSCT_P_BV1), b.Wk<float>(wb.rowpart_v1), row_part_floats(B, C), vq1_in_kernel_dw ? G(DGSCT_P_WV1) : nullptr,
-              vq1_in_kernel_dw ? b.Wk<float>(wb.vq1part) : nullptr);
+              G(DGSCT_P_BV1), b.Wk<float>(wb.rowpart_v1), row_part_floats(B, C));
       if (pj.n) defer([=, &side] { part_reduce_run(side.stream, pj); });
     } else {
     // (round 5) dX1 += dvq1 . Wv1 with dvq1 = (vq1 > 0) * E(coef_b / N) formed in the product's staging (gemm_fx.hip); d bias(vq1) from
@@ -954,7 +933,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     g2.A = mn(fx_x1 ? b.Wk(wb.dvq1) : b.S(s.vq1), C); g2.B = mn(b.S(s.X1), C);
     outF(g2, G(DGSCT_P_WV1), C);
     atomic_out(g2);
-    if (!vq1_in_kernel_dw) defer([=, &side] { wgemm(side, g2); });
+    defer([=, &side] { wgemm(side, g2); });
   }
   // B4 ---- audio queries
   {
@@ -1018,7 +997,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
       // d fc.bias = sum_{b,n} dYp[b,n,:].  Softmax rows sum to 1 and dS1 rows sum to 0, so this equals
       // sum_b (sum_t dtok[b,t,:] + da[b,:]) exactly -- computed from these two small fp32 tensors instead of
       // re-reducing the big bf16-rounded dYp (a cancellation-heavy sum: 30 % relative error in bf16 otherwise).
-      if (bias_aux) {
+      if (deferred) {
         defer([=, &side, &b] {
           const ColsumSeg segs[2] = {{b.Wk(wb.dtokF), DT_F32, B * tk, C, G(DGSCT_P_BC)}, {b.Wk(wb.da), DT_F32, B, C, G(DGSCT_P_BC)}};
           colsum_multi(side, segs, 2);
@@ -1110,7 +1089,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
         rowdot_colsum_frames(c, dYp, C, (long)N * C, B, N, C, nullptr, b.rowb(), nullptr, G(DGSCT_P_BC), b.Wk<float>(wb.rowtmp),
                              b.Wk<float>(wb.rowpart), row_part_floats(B, C));
     };
-    if (bias_aux)                                                // ... and the broadcast of d rowsum(Wc) into dWc right behind them (below)
+    if (deferred)                                                // ... and the broadcast of d rowsum(Wc) into dWc right behind them (below)
       defer([=, &side, &b] {
         bias_sums(side);
         if (conv) ew(side, EW_ADD_BCAST, G(DGSCT_P_WC), DT_F32, F32(G(DGSCT_P_WC)), F32(b.Wk(wb.dwcsum)), NOARG, (long)C * Co, 1.f, Co);
@@ -1123,8 +1102,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
   // chain of the NEXT call never waits for this call's weight gradients), on the aux stream behind them
   if (!deferred && !(SK & 8192)) stream_join(ctx);
   if (d.remap == DGSCT_REMAP_CONV) {
-    if (deferred && !bias_aux) { stream_fork(ctx); ew(side, EW_ADD_BCAST, G(DGSCT_P_WC), DT_F32, F32(G(DGSCT_P_WC)), F32(b.Wk(wb.dwcsum)), NOARG, (long)C * Co, 1.f, Co); }
-    else if (!deferred) ew(ctx, EW_ADD_BCAST, G(DGSCT_P_WC), DT_F32, F32(G(DGSCT_P_WC)), F32(b.Wk(wb.dwcsum)), NOARG, (long)C * Co, 1.f, Co);
+    if (!deferred) ew(ctx, EW_ADD_BCAST, G(DGSCT_P_WC), DT_F32, F32(G(DGSCT_P_WC)), F32(b.Wk(wb.dwcsum)), NOARG, (long)C * Co, 1.f, Co);
   }
   check_async("dgsct_adapter_backward");
   return has_error() ? 1 : 0;

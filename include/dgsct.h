@@ -343,8 +343,8 @@ int dgsct_test_gemm_fp8(int M, int N, int K, const void* A, const float* W, cons
  *   kernel; BatchNorm-2's backward inside the narrow projection's pass) off / on (default on; off = the separate launches).
  *   "gatefuse": 0 / 1 = the fused gate / bottleneck passes of the early stages (fused_gate.hip) off / on; 2 = on, and the forward
  *   also stores vq2 (for tests that read the device's ReLU decisions back).
- *   "vq1fuse": 0 / 1 = vq1 never stored at C = 96 / 128 (vq1_fwd_k / vq1_bwd_k) off / on; 2 = on + the tensor stored as well;
- *   3 = on, with dWv1 accumulated inside the backward pass (experiment, slower).  Forward and backward of one call must run
+ *   "vq1fuse": 0 / 1 = vq1 never stored at C = 96 / 128 (vq1_fwd_k / vq1_bwd_k) off / on; 2 = on + the tensor stored as well.
+ *   Forward and backward of one call must run
  *   under the same setting of "gatefuse" / "vq1fuse" (0 vs non-0): the backward of a fused forward has no stored tensor to read.
  *   "skfuse": 0 / 1 = elementwise neighbours folded into the gate-MLP products off / on.
  *   "bnfold": 0 / 1 = BatchNorm finalisation inside its consumers off / on.

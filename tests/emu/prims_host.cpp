@@ -46,8 +46,6 @@ void check_async(const char*) {}
 void clear_async() {}
 int gemm_skinny_mode(int) { return 0; }
 static int g_wgbt = 1;
-static int g_tfs8 = 1;
-int tokattn_small8_mode(int set) { const int old = g_tfs8; if (set >= 0) g_tfs8 = set ? 1 : 0; return old; }      // (a kernel-shape switch: nothing to emulate)
 int wgrad_bt_mode(int set) { const int old = g_wgbt; if (set >= 0) g_wgbt = set ? 1 : 0; return old; }
 bool wgrad_bt_supported(const Ctx&, const WgBtJob*, int n) { return g_wgbt && n >= 1 && n <= WGBT_MAX; }
 void wgrad_bt(const Ctx& ctx, const WgBtJob* jobs, int n) {          // (either element type: the host loops read through ld())
@@ -64,9 +62,6 @@ void wgrad_bt(const Ctx& ctx, const WgBtJob* jobs, int n) {          // (either 
 int gemm_tall_mode(int) { return 0; }
 int gemm8_mode(int) { return 0; }                 // (the 8-wave GEMM kernel is a device-side choice: nothing to emulate)
 int gemm_noatomic_mode(int) { return 0; }
-int gemm_cfgx_mode(int) { return 0; }
-int gemm8_wg_target(int) { return 0; }
-int gemm8_pipe_mode(int) { return 0; }
 int gemm8_stag_mode(int) { return 0; }
 
 void zero(const Ctx&, void* p, size_t bytes) { if (bytes) std::memset(p, 0, bytes); }
@@ -139,8 +134,7 @@ void gemm(const Ctx& ctx, const Gemm& g) {
 }
 
 static int g_vq1fuse = 1;
-int vq1fuse_mode(int set) { const int old = g_vq1fuse; if (set >= 0) g_vq1fuse = set > 3 ? 1 : set; return old; }
-long vq1_wpart_floats(int C) { return (long)C * C; }
+int vq1fuse_mode(int set) { const int old = g_vq1fuse; if (set >= 0) g_vq1fuse = set > 2 ? 1 : set; return old; }
 bool vq1_fused_shape(int, int, int) { return true; }                   // (host loops: any shape, either element type)
 bool vq1_fused_supported(int, int, int) { return g_vq1fuse != 0; }
 void vq1sum_fwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, int B, int N, int C, float invN, float* msum, void* vq1) {
@@ -158,11 +152,10 @@ void vq1sum_fwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv
     }
 }
 void vq1_bwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, const float* coef, int B, int N, int C, float invN,
-             void* dX1, void* dvq1_out, float* dbv1, float*, long, float* dWv1, float*) {
+             void* dX1, void* dvq1_out, float* dbv1, float*, long, float*, float*) {
   const int E = ctx.mode;
   std::vector<float> dv(C);
   std::vector<char> one_row((size_t)C * 4);
-  std::vector<double> dw(dWv1 ? (size_t)C * C : 0, 0.0);
   for (int b = 0; b < B; ++b)
     for (int n = 0; n < N; ++n) {
       const long row = (long)b * N + n;
@@ -172,9 +165,8 @@ void vq1_bwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, 
         float v = (float)acc + bv1[c] > 0.f ? invN * coef[(long)b * C + c] : 0.f;
         st(one_row.data(), E, c, v);                         // rounded to E once, as the stored tensor would be
         dv[c] = ld(one_row.data(), E, c);
-        if (!dWv1) st(dvq1_out, E, row * C + c, v);
+        st(dvq1_out, E, row * C + c, v);
         dbv1[c] += dv[c];
-        if (dWv1) for (int k = 0; k < C; ++k) dw[(size_t)c * C + k] += (double)dv[c] * ld(X1, E, row * C + k);
       }
       for (int k = 0; k < C; ++k) {
         double acc = 0;
@@ -182,7 +174,6 @@ void vq1_bwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, 
         st(dX1, E, row * C + k, ld(dX1, E, row * C + k) + (float)acc);
       }
     }
-  if (dWv1) for (size_t i = 0; i < dw.size(); ++i) dWv1[i] += (float)dw[i];
 }
 
 static int g_skfuse = 1;

@@ -51,7 +51,23 @@ def test_gemm8_isa_keeps_the_hand_ordered_reads_intact():
         pytest.skip("hipcc not available")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_gemm8_isa.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert r.stdout.count("ok   ") >= 20
+    # exactly the instantiations that exist: 4 layouts x 2 column tiles x {plain, batched, two-level}, minus the one G8_TWO_OK
+    # excludes -- a second k-loop variant coming back doubles the count
+    assert r.stdout.count("ok   ") == 23, r.stdout[-3000:]
+
+
+def test_retired_tuning_keys_are_unknown():
+    """the switches of the kernel variants that were removed are gone from dgsct_test_tune (-1: unknown key), and "vq1fuse" has no
+    mode 3 any more: a value above 2 reads back as 1, as for "gatefuse"."""
+    emu = Lib(build_emu())
+    for key in ("g8pipe", "g8wg", "cfgx", "tfs8"):
+        assert emu.test_tune(key, -1) == -1, key
+        assert emu.test_tune(key, 0) == -1, key
+    old = emu.test_tune("vq1fuse", 3)
+    try:
+        assert emu.test_tune("vq1fuse", -1) == 1
+    finally:
+        emu.test_tune("vq1fuse", old)
 
 
 def test_query_rejects_bad_descriptor():
