@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(HERE, "libdgsct.so")
 
 F32, BF16, BF16_FP8 = 0, 1, 2
 REMAP_CONV, REMAP_FIXED = 0, 1
+PATCH_IMAGE, PATCH_AUDIO = 0, 1
 
 # parameter table order == enum in include/dgsct.h; values are the reference state_dict names
 PARAM_NAMES: List[str] = [
@@ -134,6 +135,17 @@ class Lib:
         self._wattn_tables = getattr(c, "dgsct_window_attn_backward_tables", None)
         if self._wattn_tables is not None:
             self._wattn_tables.argtypes = [C.c_int] * 9 + [C.c_void_p] * 10
+        # optional (include/dgsct.h): the audio / image front ends (csrc/frontend.hip); the host emulation lacks them
+        self._logmel = getattr(c, "dgsct_logmel_forward", None)
+        self._logmel_scratch = getattr(c, "dgsct_logmel_scratch_floats", None)
+        self._patch_embed = getattr(c, "dgsct_patch_embed_forward", None)
+        if self._logmel is not None:
+            self._logmel.argtypes = [C.c_int, C.c_int64] + [C.c_int] * 3 + [C.c_void_p] * 7
+        if self._logmel_scratch is not None:
+            self._logmel_scratch.argtypes = [C.c_int, C.c_int64] + [C.c_int] * 3
+            self._logmel_scratch.restype = C.c_int64
+        if self._patch_embed is not None:
+            self._patch_embed.argtypes = [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 2
         if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
@@ -224,6 +236,28 @@ class Lib:
             raise RuntimeError(f"dg-sct_amd: {self.path} does not export dgsct_window_attn_backward_tables")
         self._check(self._wattn_tables(*geom, flags, qkv, bm, scale, out, lse, dout, dqkv, dbm, dscale, stream),
                     "dgsct_window_attn_backward_tables")
+
+    def _front_end(self, fn, name: str):
+        if fn is None:
+            raise RuntimeError(f"dg-sct_amd: {self.path} does not export {name} (a library without the audio / image front end)")
+        return fn
+
+    def logmel_scratch_floats(self, B: int, L: int, n_fft: int = 1024, hop: int = 320, n_mels: int = 64) -> int:
+        n = self._front_end(self._logmel_scratch, "dgsct_logmel_scratch_floats")(B, L, n_fft, hop, n_mels)
+        if n < 0:
+            raise RuntimeError(f"dgsct_logmel_scratch_floats failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def logmel_forward(self, B, L, waveform, melW, ranges, out, stats, scratch, stream, n_fft: int = 1024, hop: int = 320, n_mels: int = 64):
+        """pointers as ints; ranges / stats / scratch may be None (include/dgsct.h: dgsct_logmel_forward)"""
+        self._check(self._front_end(self._logmel, "dgsct_logmel_forward")(B, L, n_fft, hop, n_mels, waveform, melW, ranges, out, stats,
+                                                                           scratch, stream), "dgsct_logmel_forward")
+
+    def patch_embed_forward(self, mode, in_dtype, out_dtype, B, in_chans, H, W, T, C_, x, bn_scale, bn_shift, w, b, ln_w, ln_b, eps, out, stream):
+        """mode: PATCH_IMAGE | PATCH_AUDIO (include/dgsct.h: dgsct_patch_embed_forward)"""
+        self._check(self._front_end(self._patch_embed, "dgsct_patch_embed_forward")(mode, in_dtype, out_dtype, B, in_chans, H, W, T, C_, x,
+                                                                                     bn_scale, bn_shift, w, b, ln_w, ln_b, eps, out, stream),
+                    "dgsct_patch_embed_forward")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

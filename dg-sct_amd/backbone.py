@@ -23,6 +23,11 @@ layout (``oracle/make_golden_swinv2.py`` -> ``tests/golden/swinv2_block.pt``).
 On the GPU in bf16 (``fused=None``) the window attention of both blocks is one HIP kernel each way (``csrc/wattn.hip``; Swin-V2's q / k
 normalisation inside) and their LayerNorms (+ the post-norm residual) run on the adapter tail's row kernels (``dgsct_layer_norm_*``); the
 qkv / proj / MLP Linears and GELU stay ATen.
+
+What produces the tokens these blocks consume -- the HTS-AT STFT / log-mel / ``bn0`` / ``reshape_wav2img`` / ``patch_embed`` chain and
+``swin.patch_embed`` -- lives in ``frontend.py`` (``csrc/frontend.hip``).  Its **parity against torchlibrosa / librosa is unpinned** as well:
+neither is installed here and the oracle cannot import ``htsat.py``'s front end, so it is pinned to the published formulas in float64; a
+real checkpoint supplies its own ``melW``.
 """
 from __future__ import annotations
 

@@ -1,0 +1,380 @@
+// Audio and image front ends (the part in front of the first block): what turns a waveform / an image into the
+// patch tokens the backbone blocks consume.  Forward only: both inputs are data and both sub-modules are frozen.
+//
+//   logmel_k       waveform [B][L] -> log-mel [B][T][64], T = L / 320 + 1.  Replaces `spectrogram_extractor` + `logmel_extractor`
+//                  (DG-SCT/AVE/nets/net_trans.py:857-858; htsat.py:443-449): reflect padding, periodic Hann window, 1024-point DFT,
+//                  power, mel matrix, 10 log10(max(., 1e-10)).  One workgroup of 256 threads transforms TWO frames of one clip at a
+//                  time as the real and imaginary part of one complex 1024-point FFT (radix 4, five passes, in place in LDS, fp32,
+//                  twiddles from sincospif), separates the two spectra by their symmetry, and contracts the 513 powers with melW
+//                  over the non-zero row range of each mel column.  The power spectrogram never leaves LDS.  Optionally each
+//                  thread that writes log-mel values leaves their count, mean and sum of squared deviations (shifted sums;
+//                  logmel_stats_k combines them into mean and biased variance for `bn0` in batch-statistics mode).
+//   patch_embed_k  4 x 4 / stride 4 patch convolution + bias + LayerNorm over the embedding (layers.py:56-86).  Image mode reads
+//                  [B][in_chans][H][W]; audio mode reads the log-mel and folds `bn0` (one scale / shift per mel bin) and
+//                  `reshape_wav2img` (htsat.py:719-734: bicubic T -> 1024 along time, align_corners, A = -0.75, then the fold
+//                  image[q*64 + f][t'] = logmel[q*256 + t'][f]) into the address arithmetic of its loads.  One wavefront computes four
+//                  tokens at a time: its 64 lanes fetch the 4 x 16 pixels of the four patches (per channel), every lane owns the
+//                  embedding channels lane, lane + 64, lane + 128, pixels reach all lanes through v_readlane, the [K][C] weights sit
+//                  in LDS (read conflict-free: consecutive lanes, consecutive channels).
+//
+// The extern "C" entry points live here (not in capi.cpp): the host emulation of the CPU tests links capi.cpp against host
+// primitives and has no front end.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "../../include/dgsct.h"
+#include "prims.h"
+#include "device_util.h"
+#include "err.h"
+
+namespace dgsct {
+
+constexpr int FE_NFFT = 1024, FE_HOP = 320, FE_NMEL = 64, FE_NBIN = FE_NFFT / 2 + 1;
+constexpr int FE_MAX_T = 1024;            // reshape_wav2img takes at most spec_size * freq_ratio = 1024 frames
+constexpr int FE_LOGMEL_MAX_WG = 2048;    // 8 workgroups (19 744 B of LDS each) per CU
+
+// LDS index of FFT element i: one pad word per 32 keeps the stride-4 / stride-16 passes off a single bank
+__device__ __forceinline__ int fe_pad(int i) { return i + (i >> 5); }
+// position of X[k] after five in-place radix-4 DIF passes: the base-4 digits of k reversed
+__device__ __forceinline__ int fe_rev4(int k) {
+  const unsigned r = __brev((unsigned)k) >> 22;                 // 10 bits reversed
+  return (int)(((r & 0x155u) << 1) | ((r >> 1) & 0x155u));      // ... and the two bits of every digit swapped back
+}
+__device__ __forceinline__ int fe_reflect(int s, int L) { return s < 0 ? -s : (s >= L ? 2 * (L - 1) - s : s); }
+
+// b_m = W^(m j) * sum_p a_p (-i)^(p m): one radix-4 decimation-in-frequency butterfly; tw[n] = exp(-2 pi i n / 1024), tj = j * 1024 / span
+__device__ __forceinline__ void fe_bfly(float (&r)[4], float (&i)[4], int tj, const float2* tw) {
+  const float t0r = r[0] + r[2], t0i = i[0] + i[2], t1r = r[0] - r[2], t1i = i[0] - i[2];
+  const float t2r = r[1] + r[3], t2i = i[1] + i[3], t3r = r[1] - r[3], t3i = i[1] - i[3];
+  r[0] = t0r + t2r; i[0] = t0i + t2i;
+  const float b1r = t1r + t3i, b1i = t1i - t3r, b2r = t0r - t2r, b2i = t0i - t2i, b3r = t1r - t3i, b3i = t1i + t3r;
+  const float2 w1 = tw[tj], w2 = tw[2 * tj], w3 = tw[3 * tj];
+  r[1] = b1r * w1.x - b1i * w1.y; i[1] = b1r * w1.y + b1i * w1.x;
+  r[2] = b2r * w2.x - b2i * w2.y; i[2] = b2r * w2.y + b2i * w2.x;
+  r[3] = b3r * w3.x - b3i * w3.y; i[3] = b3r * w3.y + b3i * w3.x;
+}
+
+// part: [gridDim.x][3][128] per thread f * 64 + m (frame parity f, mel bin m): count, mean and sum of squared deviations from that mean
+// of the values it wrote (NULL: not wanted).  Accumulated as sums of v - pivot, pivot = the thread's first value: a mel bin that holds a
+// steady tone has a variance of ~0.05 dB^2 around a mean of ~20 dB, and fp32 sums of v^2 would lose it to cancellation.
+__global__ __launch_bounds__(256) void logmel_k(const float* __restrict__ wave, const float* __restrict__ melW, const int* __restrict__ ranges,
+                                                float* __restrict__ out, float* __restrict__ part, int L, int T, int npc, int npairs) {
+  __shared__ float sre[FE_NFFT + FE_NFFT / 32], sim[FE_NFFT + FE_NFFT / 32];
+  __shared__ float2 tw[768];                       // the largest twiddle index is 3 * 255
+  __shared__ float P[2][FE_NBIN + 3];
+  __shared__ float pm[2][2][FE_NMEL];
+  const int tid = threadIdx.x;
+  for (int n = tid; n < 768; n += 256) {
+    float s, c;
+    sincospif((float)n * (1.f / 512.f), &s, &c);
+    tw[n] = make_float2(c, -s);
+  }
+  float win[4];                                    // periodic Hann at this thread's four samples n = tid + 256 r
+#pragma unroll
+  for (int r = 0; r < 4; ++r) win[r] = 0.5f - 0.5f * cospif((float)(tid + 256 * r) * (1.f / 512.f));
+  // role in the mel product: frame mf, half mh of the rows, mel bin mm
+  const int mf = tid >> 7, mh = (tid >> 6) & 1, mm = tid & 63;
+  int lo = ranges ? ranges[2 * mm] : 0, hi = ranges ? ranges[2 * mm + 1] : FE_NBIN;
+  lo = lo < 0 ? 0 : lo; hi = hi > FE_NBIN ? FE_NBIN : hi;        // whatever the caller's table says, stay inside P and melW
+  float piv = 0.f, sd = 0.f, sd2 = 0.f;
+  int cnt = 0;
+  __syncthreads();
+  for (int pair = blockIdx.x; pair < npairs; pair += gridDim.x) {
+    const int b = pair / npc, t0 = (pair - b * npc) * 2;
+    const bool two = t0 + 1 < T;
+    const float* x = wave + (long)b * L;
+    float ar[4], ai[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int s0 = FE_HOP * t0 - FE_NFFT / 2 + tid + 256 * r;
+      ar[r] = x[fe_reflect(s0, L)] * win[r];
+      ai[r] = two ? x[fe_reflect(s0 + FE_HOP, L)] * win[r] : 0.f;
+    }
+    fe_bfly(ar, ai, tid, tw);                      // pass 0 (span 1024) on the loaded registers
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { sre[fe_pad(tid + 256 * m)] = ar[m]; sim[fe_pad(tid + 256 * m)] = ai[m]; }
+    __syncthreads();
+#pragma unroll
+    for (int s = 1; s < 5; ++s) {                  // spans 256, 64, 16, 4
+      const int q = 256 >> (2 * s), j = tid & (q - 1), base = (tid - j) * 4 + j;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) { ar[m] = sre[fe_pad(base + m * q)]; ai[m] = sim[fe_pad(base + m * q)]; }
+      fe_bfly(ar, ai, j << (2 * s), tw);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) { sre[fe_pad(base + m * q)] = ar[m]; sim[fe_pad(base + m * q)] = ai[m]; }
+      __syncthreads();
+    }
+    // Z = FFT(a + i b), a and b real: A[k] = (Z[k] + conj Z[N-k]) / 2, B[k] = (Z[k] - conj Z[N-k]) / 2i
+    for (int k = tid; k < FE_NBIN; k += 256) {
+      const int pk = fe_pad(fe_rev4(k)), pn = fe_pad(fe_rev4((FE_NFFT - k) & (FE_NFFT - 1)));
+      const float zr = sre[pk], zi = sim[pk], nr = sre[pn], ni = sim[pn];
+      const float a_r = zr + nr, a_i = zi - ni, b_r = zi + ni, b_i = zr - nr;
+      P[0][k] = 0.25f * (a_r * a_r + a_i * a_i);
+      P[1][k] = 0.25f * (b_r * b_r + b_i * b_i);
+    }
+    __syncthreads();
+    float acc = 0.f;
+    for (int k = lo + mh; k < hi; k += 2) acc += P[mf][k] * melW[k * FE_NMEL + mm];
+    pm[mf][mh][mm] = acc;
+    __syncthreads();
+    if (tid < 128) {
+      const int f = tid >> 6, t = t0 + f;
+      if (t < T) {
+        const float v = 10.f * log10f(fmaxf(pm[f][0][mm] + pm[f][1][mm], 1e-10f));
+        out[((long)b * T + t) * FE_NMEL + mm] = v;
+        if (cnt++ == 0) piv = v;
+        const float d = v - piv;
+        sd += d; sd2 += d * d;
+      }
+    }
+  }
+  if (part && tid < 128) {
+    const float md = cnt ? sd / (float)cnt : 0.f;
+    float* p = part + (long)blockIdx.x * 384 + tid;
+    p[0] = (float)cnt; p[128] = piv + md; p[256] = fmaxf(sd2 - sd * md, 0.f);
+  }
+}
+
+// stats[0][m] = mean, stats[1][m] = biased variance of mel bin m over all B T frames: the 2 nwg groups (count, mean, M2) of logmel_k
+// combined in double, M2 = sum_g M2_g + n_g (mean_g - mean)^2
+__global__ __launch_bounds__(1024) void logmel_stats_k(const float* __restrict__ part, int nwg, float* __restrict__ stats) {
+  __shared__ double red[2][16][64];
+  const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  double sn = 0.0, sm = 0.0;
+  for (int g = sl; g < 2 * nwg; g += 16) {
+    const float* p = part + (long)(g >> 1) * 384 + (g & 1) * 64 + c;
+    const double n = (double)p[0];
+    sn += n; sm += n * (double)p[128];
+  }
+  red[0][sl][c] = sn; red[1][sl][c] = sm;
+  __syncthreads();
+  sn = 0.0; sm = 0.0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { sn += red[0][i][c]; sm += red[1][i][c]; }
+  const double mean = sm / sn;                      // sn = B T >= 1
+  __syncthreads();
+  double m2 = 0.0;
+  for (int g = sl; g < 2 * nwg; g += 16) {
+    const float* p = part + (long)(g >> 1) * 384 + (g & 1) * 64 + c;
+    const double d = (double)p[128] - mean;
+    m2 += (double)p[256] + (double)p[0] * d * d;
+  }
+  red[0][sl][c] = m2;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    m2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m2 += red[0][i][c];
+    stats[c] = (float)mean;
+    stats[64 + c] = (float)(m2 / sn);
+  }
+}
+
+// ---- patch embedding -----------------------------------------------------------------------------------------------------------------
+struct PatchArgs {
+  const void* x; int xdt;                  // image: [B][IC][H][W] fp32 | bf16;   audio: log-mel [B][T][64] fp32
+  const float *bn_scale, *bn_shift;        // audio: [64] each
+  const float *w, *bias, *ln_w, *ln_b;     // [C][IC][4][4], [C], [C], [C]
+  void* out; int odt;                      // [B][Hp * Wp][C]
+  int H, W, Hp, Wp, C, T;
+  long tokens;                             // B * Hp * Wp
+  float eps, tscale;                       // tscale = (T - 1) / 1023 (bicubic, align_corners)
+};
+
+// PyTorch's cubic convolution coefficients (A = -0.75) for the taps at -1, 0, +1, +2 around floor(src), fraction t
+__device__ __forceinline__ void fe_cubic(float t, float (&c)[4]) {
+  constexpr float A = -0.75f;
+  const float u = 1.f - t, a = t + 1.f, d = u + 1.f;
+  c[0] = ((A * a - 5.f * A) * a + 8.f * A) * a - 4.f * A;
+  c[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
+  c[2] = ((A + 2.f) * u - (A + 3.f)) * u * u + 1.f;
+  c[3] = ((A * d - 5.f * A) * d + 8.f * A) * d - 4.f * A;
+}
+
+template <int IC, bool AUDIO, int NJ>
+__global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
+  constexpr int K = IC * 16;
+  __shared__ float Wt[K * NJ * 64];                // [k][c], c < C (rows packed at pitch C)
+  const int C = p.C, lane = threadIdx.x & 63;
+  for (int i = threadIdx.x; i < K * C; i += 256) {
+    const int c = i / K, k = i - c * K;
+    Wt[k * C + c] = p.w[i];
+  }
+  float bias[NJ], lw[NJ], lb[NJ];
+  int cw[NJ];                                      // this lane's channels, clamped for the reads (lanes past C compute and drop)
+  bool cv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    cv[j] = c < C;
+    cw[j] = cv[j] ? c : C - 1;
+    bias[j] = p.bias[cw[j]]; lw[j] = p.ln_w[cw[j]]; lb[j] = p.ln_b[cw[j]];
+  }
+  __syncthreads();
+  const int r = lane >> 4, tt = (lane >> 2) & 3, dx = lane & 3;      // this lane's pixel: row r, column dx of token tt of the group
+  const long P = (long)p.Hp * p.Wp, ngroups = (p.tokens + 3) >> 2;
+  const float invC = 1.f / (float)C;
+  for (long grp = (long)blockIdx.x * 4 + (threadIdx.x >> 6); grp < ngroups; grp += (long)gridDim.x * 4) {
+    const long tok0 = grp * 4, tok = tok0 + tt;
+    float v[IC];
+#pragma unroll
+    for (int ch = 0; ch < IC; ++ch) v[ch] = 0.f;
+    if (tok < p.tokens) {
+      const long b = tok / P;
+      const int pi = (int)(tok - b * P), pr = pi / p.Wp, pc = pi - pr * p.Wp;
+      if (AUDIO) {
+        const int f = 4 * (pr & 15) + r, tp = (pr >> 4) * 256 + 4 * pc + dx;     // image[q*64 + f][t'] = logmel'[q*256 + t'][f]
+        const float* lm = reinterpret_cast<const float*>(p.x) + b * (long)p.T * FE_NMEL + f;
+        float val;
+        if (p.T == FE_MAX_T) val = lm[(long)tp * FE_NMEL];
+        else {
+          const float src = p.tscale * (float)tp, fl = floorf(src);
+          const int i0 = (int)fl;
+          float cf[4];
+          fe_cubic(src - fl, cf);
+          val = 0.f;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            int ii = i0 - 1 + e;
+            ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
+            val += cf[e] * lm[(long)ii * FE_NMEL];
+          }
+        }
+        v[0] = val * p.bn_scale[f] + p.bn_shift[f];
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < IC; ++ch)
+          v[ch] = lde_rt(p.x, p.xdt, ((b * IC + ch) * p.H + 4 * pr + r) * (long)p.W + 4 * pc + dx);
+      }
+    }
+    float acc[4][NJ];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[t][j] = bias[j];
+#pragma unroll
+    for (int ch = 0; ch < IC; ++ch)
+#pragma unroll
+      for (int rd = 0; rd < 16; ++rd) {            // rd = row * 4 + column inside the patch
+        float w[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) w[j] = Wt[(ch * 16 + rd) * C + cw[j]];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float xv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[ch]), (rd >> 2) * 16 + t * 4 + (rd & 3)));
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[t][j] += xv * w[j];
+        }
+      }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (tok0 + t >= p.tokens) break;             // wave-uniform
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) s += cv[j] ? acc[t][j] : 0.f;
+      const float mean = group_sum(s, 64) * invC;
+      float q = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) { acc[t][j] -= mean; q += cv[j] ? acc[t][j] * acc[t][j] : 0.f; }
+      const float rstd = 1.f / sqrtf(group_sum(q, 64) * invC + p.eps);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (cv[j]) ste_rt(p.out, p.odt, (tok0 + t) * C + lane + 64 * j, acc[t][j] * rstd * lw[j] + lb[j]);
+    }
+  }
+}
+
+template <int IC, bool AUDIO, int NJ>
+static void patch_embed_launch(const PatchArgs& a, hipStream_t s) {
+  const void* fn = reinterpret_cast<const void*>(&patch_embed_k<IC, AUDIO, NJ>);
+  const long want = ((a.tokens + 3) / 4 + 3) / 4;
+  const long cap = wg_capacity(fn, 0);
+  hipLaunchKernelGGL((patch_embed_k<IC, AUDIO, NJ>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, a);
+}
+template <int IC, bool AUDIO>
+static void patch_embed_nj(const PatchArgs& a, hipStream_t s) {
+  const int nj = (a.C + 63) / 64;
+  if (nj == 1) patch_embed_launch<IC, AUDIO, 1>(a, s);
+  else if (nj == 2) patch_embed_launch<IC, AUDIO, 2>(a, s);
+  else patch_embed_launch<IC, AUDIO, 3>(a, s);
+}
+
+static int fe_logmel_wgs(int B, int64_t L) {
+  const int64_t T = L / FE_HOP + 1, npairs = (int64_t)B * ((T + 1) / 2);
+  return (int)(npairs < FE_LOGMEL_MAX_WG ? npairs : FE_LOGMEL_MAX_WG);
+}
+static bool fe_logmel_check(const char* who, int B, int64_t L, int n_fft, int hop, int n_mels) {
+  if (n_fft != FE_NFFT || hop != FE_HOP || n_mels != FE_NMEL) {
+    set_error("%s: only n_fft = 1024, hop = 320, n_mels = 64 are built (got %d, %d, %d)", who, n_fft, hop, n_mels);
+    return false;
+  }
+  if (B < 1 || L <= FE_NFFT / 2 || L / FE_HOP + 1 > FE_MAX_T || (int64_t)B * (L / FE_HOP + 1) > 0x7fffffffLL / FE_NMEL) {
+    set_error("%s: need B >= 1 and %d < L with at most %d frames (got B = %d, L = %lld)", who, FE_NFFT / 2, FE_MAX_T, B, (long long)L);
+    return false;
+  }
+  return true;
+}
+
+}  // namespace dgsct
+
+using namespace dgsct;
+
+extern "C" {
+
+int64_t dgsct_logmel_scratch_floats(int B, int64_t L, int n_fft, int hop, int n_mels) {
+  clear_error();
+  if (!fe_logmel_check("dgsct_logmel_scratch_floats", B, L, n_fft, hop, n_mels)) return -1;
+  return (int64_t)fe_logmel_wgs(B, L) * 384;
+}
+
+int dgsct_logmel_forward(int B, int64_t L, int n_fft, int hop, int n_mels, const float* waveform, const float* melW, const int32_t* ranges,
+                         float* out, float* stats, float* scratch, void* stream) {
+  clear_error();
+  if (!fe_logmel_check("dgsct_logmel_forward", B, L, n_fft, hop, n_mels)) return 2;
+  if (!waveform || !melW || !out) { set_error("dgsct_logmel_forward: NULL argument"); return 2; }
+  if (stats && !scratch) { set_error("dgsct_logmel_forward: statistics need `scratch` (dgsct_logmel_scratch_floats)"); return 2; }
+  const int T = (int)(L / FE_HOP) + 1, npc = (T + 1) / 2, npairs = B * npc, wgs = fe_logmel_wgs(B, L);
+  hipStream_t s = (hipStream_t)stream;
+  clear_async();                                   // (after the argument checks: those are pure host code)
+  hipLaunchKernelGGL(logmel_k, dim3(wgs), dim3(256), 0, s, waveform, melW, (const int*)ranges, out, stats ? scratch : nullptr, (int)L, T, npc, npairs);
+  if (stats) hipLaunchKernelGGL(logmel_stats_k, dim3(1), dim3(1024), 0, s, (const float*)scratch, wgs, stats);
+  check_async("dgsct_logmel_forward");
+  return has_error() ? 1 : 0;
+}
+
+int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
+                              const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, const float* ln_weight,
+                              const float* ln_bias, float eps, void* out, void* stream) {
+  clear_error();
+  const char* who = "dgsct_patch_embed_forward";
+  if (!x || !weight || !bias || !ln_weight || !ln_bias || !out) { set_error("%s: NULL argument", who); return 2; }
+  if ((out_dtype != DGSCT_F32 && out_dtype != DGSCT_BF16) || (in_dtype != DGSCT_F32 && in_dtype != DGSCT_BF16)) {
+    set_error("%s: dtypes must be DGSCT_F32 or DGSCT_BF16", who); return 2;
+  }
+  if (B < 1 || C < 32 || C > 192 || C % 32) { set_error("%s: need B >= 1 and C a multiple of 32 up to 192 (got %d, %d)", who, B, C); return 2; }
+  PatchArgs a{};
+  a.x = x; a.xdt = in_dtype; a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.w = weight; a.bias = bias; a.ln_w = ln_weight; a.ln_b = ln_bias;
+  a.out = out; a.odt = out_dtype; a.C = C; a.eps = eps;
+  if (mode == DGSCT_PATCH_AUDIO) {
+    if (in_chans != 1 || H != 256 || W != 256 || in_dtype != DGSCT_F32 || T < 2 || T > FE_MAX_T || !bn_scale || !bn_shift) {
+      set_error("%s: audio mode takes an fp32 log-mel of 2 .. %d frames, bn scale / shift, in_chans = 1 and a 256 x 256 image", who, FE_MAX_T);
+      return 2;
+    }
+    a.T = T; a.tscale = (float)(T - 1) / (float)(FE_MAX_T - 1);
+  } else if (mode == DGSCT_PATCH_IMAGE) {
+    if ((in_chans != 1 && in_chans != 3) || H < 4 || W < 4 || H % 4 || W % 4) {
+      set_error("%s: image mode takes in_chans 1 or 3 and H, W multiples of 4 (got %d, %d x %d)", who, in_chans, H, W); return 2;
+    }
+  } else { set_error("%s: unknown mode %d", who, mode); return 2; }
+  a.H = H; a.W = W; a.Hp = H / 4; a.Wp = W / 4;
+  a.tokens = (long)B * a.Hp * a.Wp;
+  if (a.tokens * C > 0x7fffffffffLL || (long)B * in_chans * H * W > 0x7fffffffffLL) { set_error("%s: tensor too large", who); return 2; }
+  hipStream_t s = (hipStream_t)stream;
+  clear_async();
+  if (mode == DGSCT_PATCH_AUDIO) patch_embed_nj<1, true>(a, s);
+  else if (in_chans == 1) patch_embed_nj<1, false>(a, s);
+  else patch_embed_nj<3, false>(a, s);
+  check_async(who);
+  return has_error() ? 1 : 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,233 @@
+"""What feeds the layer loop (the part in front of the first block): the reference's audio front end
+``spectrogram_extractor -> logmel_extractor -> bn0 -> reshape_wav2img -> patch_embed`` (DG-SCT/AVE/nets/net_trans.py:857-876;
+htsat.py:443-459, 719-734; layers.py:56-86) and the visual ``swin.patch_embed`` (net_trans.py:855), as two frozen, forward-only modules
+with the reference's ``state_dict`` names:
+
+    HTSATFrontEnd   waveform [B, L] -> tokens [B, 4096, embed_dim]      two or three launches of csrc/frontend.hip (ops.logmel, its
+                    statistics reduction in train mode, ops.patch_embed in audio mode); no tensor larger than the log-mel exists
+    PatchEmbed      image [B, in_chans, H, W] -> tokens [B, (H/4)(W/4), embed_dim]      one launch (ops.patch_embed)
+
+Both dispatch like the backbone blocks: ``fused=None`` runs the HIP path on GPU tensors; ``fused=False`` (or CPU tensors) runs an ATen
+formulation of the same maths (torch.stft, matmul, F.batch_norm, F.interpolate, F.conv2d, F.layer_norm) -- the CPU-testable restatement
+and the A/B partner on the GPU.
+
+**Parity against torchlibrosa / librosa is unpinned**: neither is installed here, and the oracle cannot import the front end of
+``htsat.py``.  The pin is to the published formulas evaluated in float64 (tests/test_frontend_cpu.py, tests/test_frontend_gpu.py): the
+centred, reflect-padded, periodic-Hann STFT; librosa's default (Slaney-scale, Slaney-normalised) mel filterbank; PyTorch's bicubic
+kernel.  A real HTS-AT checkpoint supplies its own ``logmel_extractor.melW``, which replaces the one built here.
+
+Out of scope: ``spec_augmenter`` and ``do_mixup`` (train-time augmentation drawn from the host RNG), ``ape`` /
+``pos_drop`` (off / identity in every reference config), the random ``crop_wav`` branch (more than 1024 frames raises here), patch
+merging and the Swin-V2 final norm."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .ops import HOP, MAX_FRAMES, N_FFT, N_MELS
+
+
+def slaney_mel_filterbank(sample_rate: int = 32000, n_fft: int = N_FFT, n_mels: int = N_MELS, fmin: float = 50.0,
+                          fmax: float = 14000.0) -> torch.Tensor:
+    """librosa.filters.mel's default (htk=False, norm='slaney') transposed to [n_fft // 2 + 1, n_mels], built in float64: triangles
+    between n_mels + 2 points evenly spaced on the Slaney mel scale (linear below 1 kHz, logarithmic above), each scaled by
+    2 / (its width in Hz)."""
+    f_sp, min_log_hz, logstep = 200.0 / 3.0, 1000.0, math.log(6.4) / 27.0
+    min_log_mel = min_log_hz / f_sp
+
+    def to_mel(f: float) -> float:
+        return f / f_sp if f < min_log_hz else min_log_mel + math.log(f / min_log_hz) / logstep
+
+    mels = torch.linspace(to_mel(fmin), to_mel(fmax), n_mels + 2, dtype=torch.float64)
+    hz = torch.where(mels < min_log_mel, mels * f_sp, min_log_hz * torch.exp(logstep * (mels - min_log_mel)))
+    bins = torch.linspace(0.0, sample_rate / 2.0, n_fft // 2 + 1, dtype=torch.float64)
+    ramps = hz[:, None] - bins[None, :]                                       # [n_mels + 2, bins]
+    fdiff = hz[1:] - hz[:-1]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    w = torch.minimum(lower, upper).clamp_min(0.0) * (2.0 / (hz[2:] - hz[:-2]))[:, None]
+    return w.t().contiguous().float()
+
+
+def hann_dft_basis(n_fft: int = N_FFT):
+    """(real, imag) [n_fft // 2 + 1, 1, n_fft] float64: the periodic-Hann-windowed DFT basis the reference's STFT convolves with
+    (`spectrogram_extractor.stft.conv_real / conv_imag`): cos(2 pi k n / N) w[n] and -sin(2 pi k n / N) w[n]"""
+    n = torch.arange(n_fft, dtype=torch.float64)
+    k = torch.arange(n_fft // 2 + 1, dtype=torch.float64)
+    win = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n / n_fft)
+    ang = 2.0 * math.pi * torch.outer(k, n) / n_fft
+    return (torch.cos(ang) * win).unsqueeze(1), (-torch.sin(ang) * win).unsqueeze(1)
+
+
+def _use_fused(fused: Optional[bool], x: torch.Tensor, who: str) -> bool:
+    if fused is None:
+        return x.is_cuda
+    if fused and not x.is_cuda:
+        raise RuntimeError(f"dg-sct_amd: {who}(fused=True) needs CUDA/HIP tensors (no CPU kernels; fused=False is the ATen formulation)")
+    return bool(fused)
+
+
+def _refuse_grad(who: str, x: torch.Tensor):
+    if x.requires_grad:
+        raise RuntimeError(f"dg-sct_amd: {who} is forward-only: its input requires grad (detach it; the front end is frozen)")
+
+
+class PatchEmbed(nn.Module):
+    """``PatchEmbed`` of timm 0.6.12 / layers.py:56-86 at patch 4, stride 4: ``norm(proj(x).flatten(2).transpose(1, 2))``; keys
+    ``proj.{weight,bias}``, ``norm.{weight,bias}``.  Frozen, forward-only.  out_dtype None: the image's dtype."""
+
+    def __init__(self, img_size, patch_size: int = 4, in_chans: int = 3, embed_dim: int = 128, fused: Optional[bool] = None, lib=None,
+                 out_dtype: Optional[torch.dtype] = None):
+        super().__init__()
+        if patch_size != 4:
+            raise ValueError("dg-sct_amd: PatchEmbed is built for 4 x 4 patches at stride 4 (every reference backbone)")
+        self.img_size = (img_size, img_size) if isinstance(img_size, int) else tuple(img_size)
+        if self.img_size[0] % 4 or self.img_size[1] % 4:
+            raise ValueError("dg-sct_amd: PatchEmbed: the image sides must be multiples of 4")
+        if in_chans not in (1, 3) or embed_dim % 32 or not 32 <= embed_dim <= 192:
+            raise ValueError("dg-sct_amd: PatchEmbed takes in_chans 1 or 3 and an embed_dim that is a multiple of 32 up to 192")
+        self.grid_size = (self.img_size[0] // 4, self.img_size[1] // 4)
+        self.num_patches = self.grid_size[0] * self.grid_size[1]
+        self.in_chans, self.embed_dim = in_chans, embed_dim
+        self.fused, self.lib, self.out_dtype = fused, lib, out_dtype
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=4, stride=4)
+        self.norm = nn.LayerNorm(embed_dim)
+        self.requires_grad_(False)
+
+    def _tokens_aten(self, img: torch.Tensor) -> torch.Tensor:
+        x = F.conv2d(img.float(), self.proj.weight, self.proj.bias, stride=4)
+        return F.layer_norm(x.flatten(2).transpose(1, 2), (self.embed_dim,), self.norm.weight, self.norm.bias, self.norm.eps)
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or x.shape[1] != self.in_chans or tuple(x.shape[2:]) != self.img_size:
+            raise RuntimeError(f"dg-sct_amd: PatchEmbed: input {tuple(x.shape)} does not match [B, {self.in_chans}, {self.img_size[0]}, {self.img_size[1]}]")
+        _refuse_grad("PatchEmbed", x)
+        out_dtype = self.out_dtype or x.dtype
+        if _use_fused(self.fused, x, "PatchEmbed"):
+            return ops.patch_embed(x.contiguous(), self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps,
+                                   out_dtype=out_dtype, lib=self.lib)
+        return self._tokens_aten(x).to(out_dtype)
+
+
+class _MelBank(nn.Module):
+    """holder of `logmel_extractor.melW` (torchlibrosa's LogmelFilterBank keeps it as a frozen Parameter)"""
+
+    def __init__(self, melW: torch.Tensor):
+        super().__init__()
+        self.melW = nn.Parameter(melW, requires_grad=False)
+
+
+class HTSATFrontEnd(nn.Module):
+    """waveform [B, L] fp32 -> HTS-AT patch tokens [B, 4096, embed_dim] (``f_a`` as the first HTS-AT block sees it, net_trans.py:857-876).
+    state_dict: ``logmel_extractor.melW`` [513, 64], ``bn0.*``, ``patch_embed.proj.*``, ``patch_embed.norm.*``; a checkpoint's
+    ``spectrogram_extractor.stft.conv_{real,imag}.weight`` are checked against the Hann-windowed DFT basis and dropped (they are functions
+    of the constants; a basis more than 1e-5 away -- entries are <= 1, so fp32 rounding plus margin -- raises; ``conv_imag`` is accepted
+    with either sign, +sin or -sin, because only the power is used).  ``bn0`` follows the module's mode: running statistics in eval mode, batch statistics
+    over (B, T) per mel bin plus the running-statistics update in train mode.  Frozen, forward-only.  out_dtype None: fp32."""
+
+    _DERIVED = ("spectrogram_extractor.stft.conv_real.weight", "spectrogram_extractor.stft.conv_imag.weight")
+
+    def __init__(self, embed_dim: int = 96, spec_size: int = 256, sample_rate: int = 32000, fmin: float = 50, fmax: float = 14000,
+                 fused: Optional[bool] = None, lib=None, out_dtype: Optional[torch.dtype] = None):
+        super().__init__()
+        if spec_size != 256:
+            raise ValueError("dg-sct_amd: HTSATFrontEnd is built for spec_size 256 (64 mel bins x 4 time quarters, every reference config)")
+        self.spec_size, self.freq_ratio = spec_size, spec_size // N_MELS
+        self.fused, self.lib, self.out_dtype = fused, lib, out_dtype
+        self.logmel_extractor = _MelBank(slaney_mel_filterbank(sample_rate, N_FFT, N_MELS, fmin, fmax))
+        self.bn0 = nn.BatchNorm2d(N_MELS)
+        self.patch_embed = PatchEmbed(spec_size, 4, 1, embed_dim, fused=fused, lib=lib, out_dtype=out_dtype)
+        self.requires_grad_(False)
+        self._ranges = None            # (melW version, device, ops.mel_ranges(melW))
+
+    # -- checkpoint loading ------------------------------------------------------------------------------------------------------------
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        basis = None
+        for name, which in zip(self._DERIVED, (0, 1)):
+            w = state_dict.pop(prefix + name, None)
+            if w is None:
+                continue
+            basis = basis or hann_dft_basis()
+            ref = basis[which]
+            ok = tuple(w.shape) == tuple(ref.shape)
+            if ok:
+                w64 = w.detach().double().cpu()
+                ok = torch.allclose(w64, ref, rtol=0.0, atol=1e-5) or (which == 1 and torch.allclose(w64, -ref, rtol=0.0, atol=1e-5))
+            if not ok:
+                error_msgs.append(f"{prefix + name} is not the periodic-Hann-windowed {N_FFT}-point DFT basis this front end computes "
+                                  f"(shape {tuple(w.shape)}); a checkpoint with another STFT cannot be loaded")
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    # -- pieces ------------------------------------------------------------------------------------------------------------------------
+    def _mel_ranges(self) -> torch.Tensor:
+        m = self.logmel_extractor.melW
+        key = (m._version, m.device, m.data_ptr())
+        if self._ranges is None or self._ranges[0] != key:
+            self._ranges = (key, ops.mel_ranges(m))
+        return self._ranges[1]
+
+    def logmel_aten(self, waveform: torch.Tensor) -> torch.Tensor:
+        """[B, L] -> [B, T, 64]: torch.stft (centred, reflect, periodic Hann), power, melW, 10 log10(max(., 1e-10))"""
+        win = torch.hann_window(N_FFT, periodic=True, dtype=waveform.dtype, device=waveform.device)
+        z = torch.stft(waveform, N_FFT, hop_length=HOP, win_length=N_FFT, window=win, center=True, pad_mode="reflect", return_complex=True)
+        power = (z.real * z.real + z.imag * z.imag).transpose(1, 2)            # [B, T, 513]
+        return 10.0 * torch.log10(torch.clamp(power @ self.logmel_extractor.melW.to(waveform.dtype), min=1e-10))
+
+    def _bn_affine(self, mean: Optional[torch.Tensor], var: Optional[torch.Tensor], n: int):
+        """scale / shift [64] of bn0 from the batch statistics (train mode: also the running-statistics update) or the running ones"""
+        bn = self.bn0
+        if mean is not None:
+            if bn.track_running_stats and bn.running_mean is not None:
+                bn.num_batches_tracked += 1
+                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+                bn.running_mean.mul_(1.0 - mom).add_(mean, alpha=mom)
+                bn.running_var.mul_(1.0 - mom).add_(var * (n / max(n - 1, 1)), alpha=mom)
+        else:
+            mean, var = bn.running_mean, bn.running_var
+        scale = bn.weight * torch.rsqrt(var + bn.eps)
+        return scale.contiguous(), (bn.bias - mean * scale).contiguous()
+
+    def _tokens_aten(self, lm: torch.Tensor) -> torch.Tensor:
+        B, T, _ = lm.shape
+        bn = self.bn0
+        x = lm.transpose(1, 2).unsqueeze(-1)                                   # [B, 64, T, 1] = the reference's `audio.transpose(1, 3)`
+        if self.training:
+            bn.num_batches_tracked += 1
+        x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps)
+        x = x.transpose(1, 3)                                                  # [B, 1, T, 64]
+        if T < MAX_FRAMES:
+            x = F.interpolate(x, (MAX_FRAMES, N_MELS), mode="bicubic", align_corners=True)
+        x = x.permute(0, 1, 3, 2).reshape(B, 1, N_MELS, self.freq_ratio, MAX_FRAMES // self.freq_ratio)
+        x = x.permute(0, 1, 3, 2, 4).reshape(B, 1, self.spec_size, self.spec_size)     # image[q*64 + f][t'] = x[q*256 + t'][f]
+        return self.patch_embed._tokens_aten(x)
+
+    @torch.no_grad()
+    def forward(self, waveform: torch.Tensor) -> torch.Tensor:
+        if waveform.dim() != 2 or waveform.dtype != torch.float32:
+            raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd takes an fp32 waveform [B, L] (got {tuple(waveform.shape)} {waveform.dtype})")
+        _refuse_grad("HTSATFrontEnd", waveform)
+        B, L = waveform.shape
+        if L <= N_FFT // 2:
+            raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd: {L} samples are too few for the reflect padding (need more than {N_FFT // 2})")
+        T = ops.logmel_frames(L)
+        if T > MAX_FRAMES:
+            raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd: {L} samples give {T} frames, more than the {MAX_FRAMES} the {self.spec_size} x "
+                               f"{self.spec_size} image holds (the reference's random crop_wav branch is not built)")
+        out_dtype = self.out_dtype or torch.float32
+        if not _use_fused(self.fused, waveform, "HTSATFrontEnd"):
+            return self._tokens_aten(self.logmel_aten(waveform)).to(out_dtype)
+        melW, pe = self.logmel_extractor.melW, self.patch_embed
+        if self.training:
+            lm, mean, var = ops.logmel(waveform.contiguous(), melW, want_stats=True, lib=self.lib, ranges=self._mel_ranges())
+            scale, shift = self._bn_affine(mean, var, B * T)
+        else:
+            lm = ops.logmel(waveform.contiguous(), melW, lib=self.lib, ranges=self._mel_ranges())
+            scale, shift = self._bn_affine(None, None, B * T)
+        return ops.patch_embed(lm, pe.proj.weight, pe.proj.bias, pe.norm.weight, pe.norm.bias, pe.norm.eps, out_dtype=out_dtype,
+                               bn_scale=scale, bn_shift=shift, lib=self.lib)

@@ -825,3 +825,125 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
         if residual.shape != x.shape or residual.dtype != x.dtype:
             raise RuntimeError("dg-sct_amd: layer_norm: residual must match x")
     return _LayerNormFn.apply(lib or default_lib(), x.contiguous(), weight.contiguous(), bias.contiguous(), eps, residual)
+
+
+# ---- audio / image front ends: waveform -> log-mel -> patch tokens (csrc/frontend.hip) ---------------------------
+N_FFT, HOP, N_MELS, MAX_FRAMES = 1024, 320, 64, 1024
+
+
+def _no_grad_inputs(who: str, *tensors):
+    """the front end is forward-only (inputs are data, parameters frozen): refuse to cut a graph silently"""
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise RuntimeError(f"dg-sct_amd: {who} is forward-only: an input requires grad (detach it; the front end's parameters are frozen)")
+
+
+def _dev_f32(who: str, name: str, t: torch.Tensor, shape, device) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"dg-sct_amd: {who}: {name} must be a contiguous fp32 tensor {tuple(shape)} on {device} (got {got})")
+    return t
+
+
+def mel_ranges(melW: torch.Tensor) -> torch.Tensor:
+    """int32 [n_mels, 2]: for every column of melW [bins, n_mels] the half-open row range outside of which it is zero (an all-zero
+    column: [0, 0)).  Summing a column's product over its range equals the dense product.  Setup-time helper (reads melW back)."""
+    nz = (melW.detach() != 0).cpu()
+    rows = torch.arange(nz.shape[0]).unsqueeze(1)
+    lo = torch.where(nz, rows, nz.shape[0]).amin(0)
+    hi = torch.where(nz, rows + 1, 0).amax(0)
+    lo = torch.minimum(lo, hi)
+    return torch.stack([lo, hi], 1).to(torch.int32).contiguous().to(melW.device)
+
+
+def logmel_frames(L: int) -> int:
+    return L // HOP + 1
+
+
+def logmel(waveform: torch.Tensor, melW: torch.Tensor, want_stats: bool = False, lib: Optional[Lib] = None,
+           ranges: Optional[torch.Tensor] = None):
+    """waveform [B, L] fp32 -> log-mel [B, T, 64] fp32, T = L // 320 + 1 (reflect-padded 1024-point Hann STFT, power, melW [513, 64],
+    10 log10(max(., 1e-10))) in one launch; the power spectrogram is never stored.  want_stats: also returns (mean [64], biased variance
+    [64]) of the log-mel over all B T frames per mel bin (one more tiny launch).  ranges: `mel_ranges(melW)` computed once by the caller
+    (None: derived here, which reads melW back to the host)."""
+    who = "logmel"
+    if not isinstance(waveform, torch.Tensor) or not waveform.is_cuda:
+        raise RuntimeError("dg-sct_amd: logmel needs CUDA/HIP tensors (no CPU fallback; HTSATFrontEnd(fused=False) is the ATen formulation)")
+    if waveform.dim() != 2 or waveform.dtype != torch.float32 or not waveform.is_contiguous():
+        raise RuntimeError(f"dg-sct_amd: logmel: waveform must be a contiguous fp32 [B, L] tensor (got {tuple(waveform.shape)} {waveform.dtype})")
+    B, L = waveform.shape
+    if B < 1 or L <= N_FFT // 2:
+        raise RuntimeError(f"dg-sct_amd: logmel: need B >= 1 and L > {N_FFT // 2} samples (reflect padding), got [{B}, {L}]")
+    T = logmel_frames(L)
+    if T > MAX_FRAMES:
+        raise RuntimeError(f"dg-sct_amd: logmel: {L} samples give {T} frames, more than the {MAX_FRAMES} the HTS-AT image holds")
+    dev = waveform.device
+    _dev_f32(who, "melW", melW, (N_FFT // 2 + 1, N_MELS), dev)
+    _no_grad_inputs(who, waveform, melW)
+    if ranges is None:
+        ranges = mel_ranges(melW)
+    if ranges.dtype != torch.int32 or tuple(ranges.shape) != (N_MELS, 2) or ranges.device != dev or not ranges.is_contiguous():
+        raise RuntimeError(f"dg-sct_amd: logmel: ranges must be a contiguous int32 [{N_MELS}, 2] tensor on {dev}")
+    lib = lib or _lib.default_lib()
+    out = torch.empty(B, T, N_MELS, dtype=torch.float32, device=dev)
+    stats = scratch = None
+    if want_stats:
+        stats = torch.empty(2, N_MELS, dtype=torch.float32, device=dev)
+        scratch = torch.empty(lib.logmel_scratch_floats(B, L), dtype=torch.float32, device=dev)
+    _mark_stream_use(waveform, melW, ranges)
+    with _dev_guard(waveform):
+        lib.logmel_forward(B, L, waveform.data_ptr(), melW.data_ptr(), ranges.data_ptr(), out.data_ptr(),
+                           stats.data_ptr() if want_stats else None, scratch.data_ptr() if want_stats else None, _stream_of(waveform))
+    return (out, stats[0], stats[1]) if want_stats else out
+
+
+def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor,
+                eps: float = 1e-5, out_dtype: Optional[torch.dtype] = None, bn_scale: Optional[torch.Tensor] = None,
+                bn_shift: Optional[torch.Tensor] = None, lib: Optional[Lib] = None) -> torch.Tensor:
+    """4 x 4 / stride-4 patch convolution + bias + LayerNorm in one launch -> tokens [B, (H/4) (W/4), C] (fp32 | bf16).
+    Image mode (bn_scale is None): x [B, in_chans, H, W] fp32 | bf16, in_chans 1 or 3.  Audio mode (bn_scale / bn_shift [64] given): x is the
+    log-mel [B, T, 64] fp32; `x * bn_scale[f] + bn_shift[f]`, the bicubic stretch of the T frames to 1024 and the fold into the 256 x 256
+    HTS-AT image are part of the kernel's loads.  weight [C, in_chans, 4, 4], bias / ln_weight / ln_bias [C] fp32; C % 32 == 0, C <= 192."""
+    who = "patch_embed"
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("dg-sct_amd: patch_embed needs CUDA/HIP tensors (no CPU fallback; PatchEmbed(fused=False) is the ATen formulation)")
+    audio = bn_scale is not None or bn_shift is not None
+    dev = x.device
+    if not x.is_contiguous():
+        raise RuntimeError("dg-sct_amd: patch_embed: x must be contiguous")
+    if audio:
+        if x.dim() != 3 or x.shape[-1] != N_MELS or x.dtype != torch.float32 or not 2 <= x.shape[1] <= MAX_FRAMES:
+            raise RuntimeError(f"dg-sct_amd: patch_embed (audio): x must be an fp32 log-mel [B, T <= {MAX_FRAMES}, {N_MELS}] (got {tuple(x.shape)} {x.dtype})")
+        B, T, in_chans, H, W = x.shape[0], x.shape[1], 1, 256, 256
+        if bn_scale is None or bn_shift is None:
+            raise RuntimeError("dg-sct_amd: patch_embed (audio): bn_scale and bn_shift go together")
+        _dev_f32(who, "bn_scale", bn_scale, (N_MELS,), dev)
+        _dev_f32(who, "bn_shift", bn_shift, (N_MELS,), dev)
+    else:
+        if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or x.shape[1] not in (1, 3) or x.shape[2] % 4 or x.shape[3] % 4 \
+                or min(x.shape[2:]) < 4:
+            raise RuntimeError(f"dg-sct_amd: patch_embed: x must be fp32 / bf16 [B, 1 | 3, H, W] with H, W multiples of 4 (got {tuple(x.shape)} {x.dtype})")
+        B, in_chans, H, W = x.shape
+        T = 0
+    if B < 1:
+        raise RuntimeError("dg-sct_amd: patch_embed: empty batch")
+    C_ = weight.shape[0] if isinstance(weight, torch.Tensor) and weight.dim() == 4 else 0
+    if C_ < 32 or C_ > 192 or C_ % 32:
+        raise RuntimeError(f"dg-sct_amd: patch_embed: the embedding width must be a multiple of 32 up to 192 (weight {tuple(getattr(weight, 'shape', ()))})")
+    _dev_f32(who, "weight", weight, (C_, in_chans, 4, 4), dev)
+    for n, t in (("bias", bias), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        _dev_f32(who, n, t, (C_,), dev)
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("dg-sct_amd: patch_embed: out_dtype must be float32 or bfloat16")
+    _no_grad_inputs(who, x, weight, bias, ln_weight, ln_bias, bn_scale, bn_shift)
+    lib = lib or _lib.default_lib()
+    out = torch.empty(B, (H // 4) * (W // 4), C_, dtype=out_dtype, device=dev)
+    code = lambda dt: _lib.F32 if dt == torch.float32 else _lib.BF16
+    _mark_stream_use(x, weight, bias, ln_weight, ln_bias, bn_scale, bn_shift)
+    with _dev_guard(x):
+        lib.patch_embed_forward(_lib.PATCH_AUDIO if audio else _lib.PATCH_IMAGE, code(x.dtype), code(out_dtype), B, in_chans, H, W, T, C_,
+                                x.data_ptr(), bn_scale.data_ptr() if audio else None, bn_shift.data_ptr() if audio else None,
+                                weight.data_ptr(), bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps), out.data_ptr(),
+                                _stream_of(x))
+    return out

@@ -257,6 +257,37 @@ int dgsct_layer_norm_forward(int dtype, int64_t rows, int C, const void* x, cons
 int dgsct_layer_norm_backward(int dtype, int64_t rows, int C, const void* dout, const void* x, const float* w, const float* b, const float* mu,
                               const float* rstd, float eps, void* dx, float* dw, float* db, float* scratch, void* stream);
 
+/* ---- audio / image front ends: waveform -> log-mel -> patch tokens (csrc/frontend.hip) ----------------------
+ * Forward only (inputs are data, the sub-modules are frozen).  Optional exports: a library built without csrc/frontend.hip (the host
+ * emulation of the CPU tests) leaves them undefined, so bind them by name.
+ *
+ * dgsct_logmel_forward replaces `spectrogram_extractor` + `logmel_extractor` (DG-SCT/AVE/nets/net_trans.py:857-858, htsat.py:443-449):
+ *   waveform [B][L] fp32 -> out [B][T][64] fp32, T = L / hop + 1: frame t = samples [hop t - n_fft/2, hop t + n_fft/2) of the signal
+ *   reflect-padded by n_fft/2 (-i -> i, L-1+i -> L-1-i), periodic Hann window, 1024-point DFT (fp32 radix-4 FFT in LDS), power of bins
+ *   0 .. 512, product with melW [513][64] (fp32, a checkpoint entry), 10 log10(max(., 1e-10)).  The power spectrogram is never stored.
+ *   ranges: int32 [64][2] = for every mel column the half-open row range outside of which melW is zero (NULL: all 513 rows);
+ *   stats : NULL, or fp32 [2][64] = per mel bin the mean and the BIASED variance of `out` over all B T frames (`bn0` in batch-statistics
+ *           mode); then `scratch` must hold dgsct_logmel_scratch_floats(...) floats (per-thread count / mean / squared deviations, combined by a second launch).
+ *   Only n_fft = 1024, hop = 320, n_mels = 64 are built (esc_config.py:48-54: every reference task); B >= 1, n_fft/2 < L, T <= 1024.
+ *
+ * dgsct_patch_embed_forward replaces `patch_embed` of either backbone (layers.py:56-86: Conv2d(in_chans, C, 4, stride 4) + flatten +
+ * LayerNorm(C)): out [B][(H/4) (W/4)][C], token index = patch row * (W/4) + patch column, out_dtype DGSCT_F32 | DGSCT_BF16;
+ * weight [C][in_chans][4][4], bias / ln_weight / ln_bias [C] fp32; C a multiple of 32, 32 .. 192.
+ *   DGSCT_PATCH_IMAGE: x = [B][in_chans][H][W] (in_dtype DGSCT_F32 | DGSCT_BF16), in_chans 1 or 3, H and W multiples of 4; T, bn_* unused.
+ *   DGSCT_PATCH_AUDIO: x = the log-mel [B][T][64] fp32 (T <= 1024), H = W = 256, in_chans = 1.  `bn0` (net_trans.py:860) enters as
+ *     bn_scale / bn_shift [64] (x * scale[f] + shift[f]), and `reshape_wav2img` (htsat.py:719-734) is address arithmetic of the loads:
+ *     bicubic interpolation along time T -> 1024 (align_corners, A = -0.75, taps clamped; a plain copy when T == 1024), then
+ *     image[q*64 + f][t'] = logmel'[q*256 + t'][f].  Neither the interpolated tensor nor the image exists in memory.
+ * Asynchronous on `stream`; 0 or an error code (dgsct_logmel_scratch_floats: -1). */
+#define DGSCT_PATCH_IMAGE 0
+#define DGSCT_PATCH_AUDIO 1
+int64_t dgsct_logmel_scratch_floats(int B, int64_t L, int n_fft, int hop, int n_mels);
+int dgsct_logmel_forward(int B, int64_t L, int n_fft, int hop, int n_mels, const float* waveform, const float* melW, const int32_t* ranges,
+                         float* out, float* stats, float* scratch, void* stream);
+int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
+                              const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, const float* ln_weight,
+                              const float* ln_bias, float eps, void* out, void* stream);
+
 /* ---- gate application of the post-backbone TemporalAttention ---------------------------
  * Replaces the tail of `TemporalAttention.forward` (DG-SCT/AVE/nets/net_trans.py:240-251; AVVP nets/mgn.py:148-159):
  *   audio_gate = audio_gated(audio_key_value_feature); video_gate = video_gated(video_key_value_feature)     [T,B,1]

@@ -1,0 +1,93 @@
+"""Timing of the audio / image front ends (csrc/frontend.hip) at the AVE shapes: 160 waveforms of 320 000 samples -> HTS-AT tokens, and
+160 images of 3 x 192 x 192 -> Swin-V2 tokens, each against the module's own fused=False ATen formulation on the same GPU.
+Method: 3 warm-up calls, then `--reps` windows of `--inner` calls between two device events; the median window is reported (min / max
+beside it).  Traffic floor of the audio path: waveform in, log-mel out and back in, tokens out.
+usage: python tools/frontend_bench.py [--batch 160] [--samples 320000] [--reps 7] [--inner 5] [--embed-dim 96]"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import dgsct_amd  # noqa: E402,F401
+from dgsct_amd import HTSATFrontEnd, PatchEmbed, ops  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=160)
+ap.add_argument("--samples", type=int, default=320000)
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--inner", type=int, default=5)
+ap.add_argument("--embed-dim", type=int, default=96)
+args = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("frontend_bench: needs a GPU (a timing taken elsewhere says nothing)")
+dev = torch.device("cuda:0")
+
+
+def timed(fn):
+    """(median, min, max) in microseconds per call"""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) / args.inner * 1e3)
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def row(name, t, nbytes=None):
+    med, lo, hi = t
+    extra = f"   {nbytes / 1e6:8.1f} MB  {nbytes / med / 1e3:7.0f} GB/s" if nbytes else ""
+    print(f"{name:<58} {med:10.1f} us  (min {lo:.1f}, max {hi:.1f}){extra}", flush=True)
+    return med
+
+
+B, L, C = args.batch, args.samples, args.embed_dim
+T = L // 320 + 1
+gen = torch.Generator().manual_seed(0)
+wave = (0.1 * torch.randn(B, L, generator=gen)).to(dev)
+print(f"audio: waveform [{B}, {L}] fp32 -> {T} frames -> tokens [{B}, 4096, {C}]; {torch.cuda.get_device_name(0)}")
+for out_dtype in (torch.bfloat16, torch.float32):
+    for training in (False, True):
+        m = HTSATFrontEnd(embed_dim=C, out_dtype=out_dtype).to(dev).train(training)
+        a = HTSATFrontEnd(embed_dim=C, out_dtype=out_dtype, fused=False).to(dev).train(training)
+        melW, rng, pe = m.logmel_extractor.melW, m._mel_ranges(), m.patch_embed
+        lm = ops.logmel(wave, melW, ranges=rng)
+        sc, sh = m._bn_affine(None, None, B * T)
+        es = 2 if out_dtype == torch.bfloat16 else 4
+        by_lm, by_pe = B * L * 4 + B * T * 64 * 4, B * T * 64 * 4 + B * 4096 * C * es
+        tag = f"[{'bf16' if es == 2 else 'fp32'} tokens, {'train' if training else 'eval'}]"
+        if training:
+            t_lm = row(f"{tag} HIP logmel + statistics (2 launches)", timed(lambda: ops.logmel(wave, melW, want_stats=True, ranges=rng)), by_lm)
+        else:
+            t_lm = row(f"{tag} HIP logmel (1 launch)", timed(lambda: ops.logmel(wave, melW, ranges=rng)), by_lm)
+        t_pe = row(f"{tag} HIP patch_embed, audio mode (1 launch)",
+                   timed(lambda: ops.patch_embed(lm, pe.proj.weight, pe.proj.bias, pe.norm.weight, pe.norm.bias, 1e-5, out_dtype, sc, sh)), by_pe)
+        t_f = row(f"{tag} HIP end to end (module call)", timed(lambda: m(wave)), by_lm + by_pe)
+        t_a = row(f"{tag} ATen formulation (fused=False), same GPU", timed(lambda: a(wave)))
+        print(f"{tag} fused / ATen = {t_f / t_a:.3f}  (ATen / fused = {t_a / t_f:.2f} x);  traffic floor {(by_lm + by_pe) / 1e9:.3f} GB at 8 TB/s = "
+              f"{(by_lm + by_pe) / 8e6:.1f} us -> achieved fraction {(by_lm + by_pe) / 8e6 / t_f:.3f}\n", flush=True)
+        del m, a, lm
+        torch.cuda.empty_cache()
+
+del wave
+torch.cuda.empty_cache()
+for in_dtype in (torch.bfloat16, torch.float32):
+    for Cv in (128, 192):
+        img = torch.randn(B, 3, 192, 192, generator=gen).to(dev, in_dtype)
+        m = PatchEmbed(192, in_chans=3, embed_dim=Cv, out_dtype=torch.bfloat16).to(dev)
+        a = PatchEmbed(192, in_chans=3, embed_dim=Cv, out_dtype=torch.bfloat16, fused=False).to(dev)
+        nb = img.numel() * img.element_size() + B * 2304 * Cv * 2
+        tag = f"[image {B} x 3 x 192 x 192 {'bf16' if in_dtype == torch.bfloat16 else 'fp32'} -> bf16 tokens, C = {Cv}]"
+        t_f = row(f"{tag} HIP", timed(lambda: m(img)), nb)
+        t_a = row(f"{tag} ATen", timed(lambda: a(img)))
+        print(f"{tag} ATen / fused = {t_a / t_f:.2f} x;  floor at 8 TB/s {nb / 8e6:.1f} us -> achieved fraction {nb / 8e6 / t_f:.3f}\n", flush=True)
