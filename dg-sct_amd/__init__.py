@@ -11,3 +11,4 @@ from .dp import GradAllReducer, init_process_group                 # noqa: F401
 from .temporal import TemporalAttention, TemporalAttentionAVS, TemporalAttentionAVVP, frame_scale   # noqa: F401
 from .backbone import FrozenBlocks, HTSATBlock, SwinV2Block         # noqa: F401
 from .frontend import HTSATFrontEnd, PatchEmbed                     # noqa: F401
+from .merging import AVETrunk, HTSATPatchMerging, SwinV2PatchMerging   # noqa: F401

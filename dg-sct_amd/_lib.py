@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libdgsct.so")
 F32, BF16, BF16_FP8 = 0, 1, 2
 REMAP_CONV, REMAP_FIXED = 0, 1
 PATCH_IMAGE, PATCH_AUDIO = 0, 1
+PMERGE_NORM_FIRST, PMERGE_NORM_LAST = 0, 1
 
 # parameter table order == enum in include/dgsct.h; values are the reference state_dict names
 PARAM_NAMES: List[str] = [
@@ -146,6 +147,17 @@ class Lib:
             self._logmel_scratch.restype = C.c_int64
         if self._patch_embed is not None:
             self._patch_embed.argtypes = [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 2
+        # optional (include/dgsct.h): patch merging between two stages (csrc/pmerge.hip); the host emulation lacks it
+        self._pmerge_ws = getattr(c, "dgsct_patch_merge_ws_bytes", None)
+        self._pmerge_fwd = getattr(c, "dgsct_patch_merge_forward", None)
+        self._pmerge_bwd = getattr(c, "dgsct_patch_merge_backward", None)
+        if self._pmerge_ws is not None:
+            self._pmerge_ws.argtypes = [C.c_int] * 5
+            self._pmerge_ws.restype = C.c_int64
+        if self._pmerge_fwd is not None:
+            self._pmerge_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5
+        if self._pmerge_bwd is not None:
+            self._pmerge_bwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3
         if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
@@ -258,6 +270,31 @@ class Lib:
         self._check(self._front_end(self._patch_embed, "dgsct_patch_embed_forward")(mode, in_dtype, out_dtype, B, in_chans, H, W, T, C_, x,
                                                                                      bn_scale, bn_shift, w, b, ln_w, ln_b, eps, out, stream),
                     "dgsct_patch_embed_forward")
+
+    @property
+    def has_patch_merge(self) -> bool:
+        """whether this library exports dgsct_patch_merge_* (csrc/pmerge.hip)"""
+        return None not in (self._pmerge_ws, self._pmerge_fwd, self._pmerge_bwd)
+
+    def _pmerge(self, fn, name: str):
+        if fn is None:
+            raise RuntimeError(f"dg-sct_amd: {self.path} does not export {name} (a library without patch merging)")
+        return fn
+
+    def patch_merge_ws_bytes(self, mode: int, B: int, H: int, W: int, C_: int) -> int:
+        n = self._pmerge(self._pmerge_ws, "dgsct_patch_merge_ws_bytes")(mode, B, H, W, C_)
+        if n < 0:
+            raise RuntimeError(f"dgsct_patch_merge_ws_bytes failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def patch_merge_forward(self, mode, B, H, W, C_, x, w_bf16, ln_w, ln_b, eps, out, pre, mu, rstd, stream):
+        """pointers as ints; pre: NORM_LAST only, else None (include/dgsct.h: dgsct_patch_merge_forward)"""
+        self._check(self._pmerge(self._pmerge_fwd, "dgsct_patch_merge_forward")(mode, B, H, W, C_, x, w_bf16, ln_w, ln_b, eps, out, pre, mu,
+                                                                                 rstd, stream), "dgsct_patch_merge_forward")
+
+    def patch_merge_backward(self, mode, B, H, W, C_, dout, x, w_bf16, ln_w, pre, mu, rstd, eps, dx, ws, stream):
+        self._check(self._pmerge(self._pmerge_bwd, "dgsct_patch_merge_backward")(mode, B, H, W, C_, dout, x, w_bf16, ln_w, pre, mu, rstd, eps,
+                                                                                  dx, ws, stream), "dgsct_patch_merge_backward")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

@@ -17,8 +17,8 @@ centred, reflect-padded, periodic-Hann STFT; librosa's default (Slaney-scale, Sl
 kernel.  A real HTS-AT checkpoint supplies its own ``logmel_extractor.melW``, which replaces the one built here.
 
 Out of scope: ``spec_augmenter`` and ``do_mixup`` (train-time augmentation drawn from the host RNG), ``ape`` /
-``pos_drop`` (off / identity in every reference config), the random ``crop_wav`` branch (more than 1024 frames raises here), patch
-merging and the Swin-V2 final norm."""
+``pos_drop`` (off / identity in every reference config), the random ``crop_wav`` branch (more than 1024 frames raises here).  Patch merging
+and the Swin-V2 final norm live in ``merging.py`` (``AVETrunk``)."""
 from __future__ import annotations
 
 import math

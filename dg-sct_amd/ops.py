@@ -662,7 +662,7 @@ def map_pool(f: torch.Tensor, spatial_att_maps: torch.Tensor, lib: Optional[Lib]
     """Drop-in for `torch.bmm(spatial_att_maps, f)` at the end of the reference's layer loop
     (DG-SCT/AVE/nets/net_trans.py:922-924): f [BT,N,C] (fp32 | bf16), spatial_att_maps [BT,1,N] (the second output of the
     last p2 adapter) -> [BT,1,C] in f's dtype.  One HIP reduction forward, two kernels backward (dgsct_map_pool_*)."""
-    if not f.is_cuda:
+    if not f.is_cuda and lib is None:                     # (CPU tensors with lib=: the host emulation of the tests, nothing else)
         raise RuntimeError("dg-sct_amd: map_pool needs CUDA/HIP tensors (no CPU fallback)")
     BT, N, C_ = f.shape
     if spatial_att_maps.shape not in ((BT, 1, N), (BT, N)):
@@ -947,3 +947,81 @@ def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_we
                                 weight.data_ptr(), bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps), out.data_ptr(),
                                 _stream_of(x))
     return out
+
+
+# ---- patch merging between two backbone stages (csrc/pmerge.hip) ------------------------------------------------
+PMERGE_NORM_FIRST, PMERGE_NORM_LAST = _lib.PMERGE_NORM_FIRST, _lib.PMERGE_NORM_LAST
+
+
+def patch_merge_supported(x: torch.Tensor, H: int, W: int, mode: int) -> bool:
+    """what csrc/pmerge.hip takes: a bf16 GPU map [B, H*W, C], H and W even, C a multiple of 32 with 4C <= 1536 (NORM_FIRST) /
+    2C <= 1536 (NORM_LAST)"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 3 or x.shape[0] < 1:
+        return False
+    C_ = x.shape[-1]
+    return (H >= 2 and W >= 2 and H % 2 == 0 and W % 2 == 0 and x.shape[1] == H * W and C_ >= 32 and C_ % 32 == 0
+            and C_ <= (384 if mode == PMERGE_NORM_FIRST else 768))
+
+
+class _PatchMergeFn(torch.autograd.Function):
+    """one library call each way (dgsct_patch_merge_*); gradient for x only: the merges are frozen"""
+
+    @staticmethod
+    def forward(ctx, lib, x, w, ln_w, ln_b, eps, H, W, mode):
+        B, L, C_ = x.shape
+        rows = B * (H // 2) * (W // 2)
+        out = torch.empty(B, rows // B, 2 * C_, dtype=x.dtype, device=x.device)
+        pre = torch.empty_like(out) if mode == PMERGE_NORM_LAST else None
+        mu = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _mark_stream_use(x, w, ln_w, ln_b)
+        with _dev_guard(x):
+            lib.patch_merge_forward(mode, B, H, W, C_, x.data_ptr(), w.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps), out.data_ptr(),
+                                    pre.data_ptr() if pre is not None else None, mu.data_ptr(), rstd.data_ptr(), _stream_of(x))
+        ctx.lib, ctx.geom, ctx.eps = lib, (mode, B, H, W, C_), float(eps)
+        # NORM_FIRST's backward re-gathers x; NORM_LAST's reads `pre` instead, so the stage map is not kept alive for it
+        ctx.save_for_backward(w, ln_w, mu, rstd, x if pre is None else pre)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        w, ln_w, mu, rstd, kept = ctx.saved_tensors
+        mode, B, H, W, C_ = ctx.geom
+        x, pre = (kept, None) if mode == PMERGE_NORM_FIRST else (None, kept)
+        dout = dout.contiguous()
+        if dout.dtype != kept.dtype:
+            dout = dout.to(kept.dtype)
+        dx = torch.empty(B, H * W, C_, dtype=kept.dtype, device=kept.device)
+        ws = torch.empty(ctx.lib.patch_merge_ws_bytes(*ctx.geom), dtype=torch.uint8, device=kept.device)
+        _mark_stream_use(kept, w, ln_w, mu, rstd, dout)
+        with _dev_guard(kept):
+            ctx.lib.patch_merge_backward(*ctx.geom, dout.data_ptr(), x.data_ptr() if x is not None else None, w.data_ptr(), ln_w.data_ptr(),
+                                         pre.data_ptr() if pre is not None else None, mu.data_ptr(), rstd.data_ptr(), ctx.eps, dx.data_ptr(),
+                                         ws.data_ptr(), _stream_of(kept))
+        return None, dx, None, None, None, None, None, None, None
+
+
+def patch_merge(x: torch.Tensor, w_bf16: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float, H: int, W: int, mode: int,
+                lib: Optional[Lib] = None) -> torch.Tensor:
+    """The 2 x 2 patch merge between two stages on x [B, H*W, C] (bf16, token-major) -> [B, (H/2)(W/2), 2C]:
+    PMERGE_NORM_FIRST (HTS-AT) `LN_4C(gather(x)) @ w^T`, PMERGE_NORM_LAST (Swin-V2) `LN_2C(gather(x) @ w^T)`; gather = the four tokens
+    (2i,2j), (2i+1,2j), (2i,2j+1), (2i+1,2j+1) side by side.  w_bf16 [2C, 4C] bf16, ln_w / ln_b fp32 ([4C] / [2C]).  One launch forward
+    (NORM_LAST: two), two backward; the gradient reaches x only (w and the norm vectors are frozen inputs)."""
+    who = "patch_merge"
+    if mode not in (PMERGE_NORM_FIRST, PMERGE_NORM_LAST):
+        raise RuntimeError(f"dg-sct_amd: {who}: unknown mode {mode}")
+    if not patch_merge_supported(x, H, W, mode):
+        raise RuntimeError(f"dg-sct_amd: {who} takes a bf16 CUDA/HIP map [B, H*W, C] with H, W even, C a multiple of 32 and "
+                           f"{'4C' if mode == PMERGE_NORM_FIRST else '2C'} <= 1536 (got {tuple(getattr(x, 'shape', ()))} "
+                           f"{getattr(x, 'dtype', None)}, map {H} x {W}; no CPU kernels: fused=False is the ATen formulation)")
+    C_ = x.shape[-1]
+    dev = x.device
+    if (not isinstance(w_bf16, torch.Tensor) or w_bf16.dtype != torch.bfloat16 or tuple(w_bf16.shape) != (2 * C_, 4 * C_) or w_bf16.device != dev
+            or not w_bf16.is_contiguous()):
+        raise RuntimeError(f"dg-sct_amd: {who}: w_bf16 must be a contiguous bf16 tensor [{2 * C_}, {4 * C_}] on {dev}")
+    cn = 4 * C_ if mode == PMERGE_NORM_FIRST else 2 * C_
+    _dev_f32(who, "ln_w", ln_w, (cn,), dev)
+    _dev_f32(who, "ln_b", ln_b, (cn,), dev)
+    if any(t.requires_grad for t in (w_bf16, ln_w, ln_b)):
+        raise RuntimeError(f"dg-sct_amd: {who} returns no weight gradients: pass detached w_bf16 / ln_w / ln_b (a trainable merge takes the ATen formulation)")
+    return _PatchMergeFn.apply(lib or _lib.default_lib(), x.contiguous(), w_bf16, ln_w, ln_b, float(eps), int(H), int(W), int(mode))

@@ -288,6 +288,28 @@ int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int 
                               const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, const float* ln_weight,
                               const float* ln_bias, float eps, void* out, void* stream);
 
+/* ---- patch merging between two backbone stages (csrc/pmerge.hip) -----------------------------------------------------------------
+ * The 2 x 2 merge of `f_v = my_blk.downsample(f_v)` / `f_a = htsat_blk.downsample(f_a)` (DG-SCT/AVE/nets/net_trans.py:914-916).  Optional
+ * exports, like the front ends: bind them by name.
+ *   x [B][H*W][C] bf16, token-major; output row r = (b, i, j), i < H/2, j < W/2, is made from the virtual 4C-wide row
+ *   cat(x[b][2i][2j], x[b][2i+1][2j], x[b][2i][2j+1], x[b][2i+1][2j+1]) (never stored by a forward) and w_bf16 [2C][4C] (bf16, no bias):
+ *   DGSCT_PMERGE_NORM_FIRST (HTS-AT, htsat.py:259-295): out = LN_4C(row) . w^T; ln_w / ln_b fp32 [4C]; one launch; mu / rstd fp32 [rows]
+ *     are the row statistics over 4C; `pre` unused (NULL).
+ *   DGSCT_PMERGE_NORM_LAST (Swin-V2, timm 0.6.12 PatchMerging): out = LN_2C(row . w^T); ln_w / ln_b fp32 [2C]; two launches; `pre`
+ *     [rows][2C] bf16 receives the product before the norm (kept for backward), mu / rstd its row statistics.
+ *   out [B][(H/2)(W/2)][2C] bf16.  The same rounding points as LayerNorm and Linear in bf16, one after the other.
+ * backward: dx [B][H*W][C] bf16 only (the merges are frozen: no parameter gradients), every element written exactly once, two launches;
+ *   ws: dgsct_patch_merge_ws_bytes(...) bytes of scratch.  NORM_FIRST reads x (pre NULL), NORM_LAST reads pre (x may be NULL).
+ * Limits: H, W even and >= 2; C a multiple of 32, >= 32; 4C <= 1536 (NORM_FIRST), 2C <= 1536 (NORM_LAST); bf16 only.
+ * Asynchronous on `stream`; 0 or an error code (dgsct_patch_merge_ws_bytes: -1). */
+#define DGSCT_PMERGE_NORM_FIRST 0
+#define DGSCT_PMERGE_NORM_LAST  1
+int64_t dgsct_patch_merge_ws_bytes(int mode, int B, int H, int W, int C);
+int dgsct_patch_merge_forward(int mode, int B, int H, int W, int C, const void* x, const void* w_bf16, const float* ln_w, const float* ln_b,
+                              float eps, void* out, void* pre /* NORM_LAST only, else NULL */, float* mu, float* rstd, void* stream);
+int dgsct_patch_merge_backward(int mode, int B, int H, int W, int C, const void* dout, const void* x, const void* w_bf16, const float* ln_w,
+                               const void* pre, const float* mu, const float* rstd, float eps, void* dx, void* ws, void* stream);
+
 /* ---- gate application of the post-backbone TemporalAttention ---------------------------
  * Replaces the tail of `TemporalAttention.forward` (DG-SCT/AVE/nets/net_trans.py:240-251; AVVP nets/mgn.py:148-159):
  *   audio_gate = audio_gated(audio_key_value_feature); video_gate = video_gated(video_key_value_feature)     [T,B,1]
