@@ -158,6 +158,14 @@ class Lib:
             self._pmerge_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5
         if self._pmerge_bwd is not None:
             self._pmerge_bwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 3
+        # optional (include/dgsct.h): the merge's backward with parameter gradients, for a trainable merge
+        self._pmerge_pws = getattr(c, "dgsct_patch_merge_params_ws_bytes", None)
+        self._pmerge_bwd_params = getattr(c, "dgsct_patch_merge_backward_params", None)
+        if self._pmerge_pws is not None:
+            self._pmerge_pws.argtypes = [C.c_int] * 5
+            self._pmerge_pws.restype = C.c_int64
+        if self._pmerge_bwd_params is not None:
+            self._pmerge_bwd_params.argtypes = [C.c_int] * 5 + [C.c_void_p] * 8 + [C.c_float] + [C.c_void_p] * 6
         if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
@@ -295,6 +303,23 @@ class Lib:
     def patch_merge_backward(self, mode, B, H, W, C_, dout, x, w_bf16, ln_w, pre, mu, rstd, eps, dx, ws, stream):
         self._check(self._pmerge(self._pmerge_bwd, "dgsct_patch_merge_backward")(mode, B, H, W, C_, dout, x, w_bf16, ln_w, pre, mu, rstd, eps,
                                                                                   dx, ws, stream), "dgsct_patch_merge_backward")
+
+    def has_patch_merge_params(self) -> bool:
+        """whether this library exports dgsct_patch_merge_backward_params / dgsct_patch_merge_params_ws_bytes (the weight and norm gradients
+        of a trainable merge) on top of dgsct_patch_merge_*"""
+        return self.has_patch_merge and None not in (self._pmerge_pws, self._pmerge_bwd_params)
+
+    def patch_merge_params_ws_bytes(self, mode: int, B: int, H: int, W: int, C_: int) -> int:
+        n = self._pmerge(self._pmerge_pws, "dgsct_patch_merge_params_ws_bytes")(mode, B, H, W, C_)
+        if n < 0:
+            raise RuntimeError(f"dgsct_patch_merge_params_ws_bytes failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def patch_merge_backward_params(self, mode, B, H, W, C_, dout, x, w_bf16, ln_w, ln_b, pre, mu, rstd, eps, dx, dw, dln_w, dln_b, ws, stream):
+        """dx as patch_merge_backward (bit for bit) + dw [2C, 4C] / dln_w / dln_b in fp32, zeroed by the call; NORM_LAST needs x AND pre
+        (include/dgsct.h: dgsct_patch_merge_backward_params)"""
+        self._check(self._pmerge(self._pmerge_bwd_params, "dgsct_patch_merge_backward_params")(
+            mode, B, H, W, C_, dout, x, w_bf16, ln_w, ln_b, pre, mu, rstd, eps, dx, dw, dln_w, dln_b, ws, stream), "dgsct_patch_merge_backward_params")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

@@ -20,6 +20,9 @@
 //     backward            pm_lnbwd_k<false>: dpre = LN backward of dout over 2C from pre / mu / rstd -> ws [rows][2C] bf16;
 //                         pm_dgemm_k<true>: dx = dpre . W with the scatter as the store addressing of the epilogue.
 //   Every element of dx is written exactly once (the 2 x 2 cells do not overlap): no atomics, no pre-zeroing.
+//   A TRAINABLE merge (dgsct_patch_merge_backward_params): the same launches with pm_lnbwd_sums_k in the place of pm_lnbwd_k -- the same
+//   row arithmetic, so dx is bit for bit the same, plus the column sums d ln_w / d ln_b -- and pm_wgrad_k for dW [2C][4C] = D^T . A with
+//   the A operand staged from the token map (fp32 atomics over at most 40 row slabs).  All three gradients fp32, zeroed by the call.
 //
 // Limits (enforced below): H, W even and >= 2; C % 32 == 0, C >= 32; 4C <= 1536 (NORM_FIRST) / 2C <= 1536 (NORM_LAST); bf16 only.
 // Global loads that can run past the last row are UNCONDITIONAL from clamped addresses and masked in the register.
@@ -257,13 +260,12 @@ __global__ __launch_bounds__(256) void pm_dgemm_k(PmGeom g, const void* __restri
 // ---- LayerNorm backward over rows of Cn channels, one wavefront per row --------------------------------------------------------------
 // dx = rstd (dy w - mean(dy w) - x^ mean(dy w x^)), x^ = (x - mu) rstd.  GATHER: x is the token map, the row is its virtual 4C row and dx
 // is scattered to the four tokens; otherwise x (= pre) and dx are plain [rows][Cn].
-template <bool GATHER, int NIT>
-__global__ __launch_bounds__(256) void pm_lnbwd_k(PmGeom g, int Cn, const void* __restrict__ dy, const void* __restrict__ xs,
-                                                  const float* __restrict__ ln_w, const float* __restrict__ mu, const float* __restrict__ rstd,
-                                                  void* __restrict__ dx) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= g.rows) return;                         // (no barrier in this kernel)
+// One row.  SUMS: the lane also adds dy x^ and dy (dy BEFORE the multiplication with ln_w) into its per-channel sums sw / sb, the
+// row's terms of d ln_w / d ln_b; what reaches dx is the same arithmetic with and without.
+template <bool GATHER, int NIT, bool SUMS>
+__device__ __forceinline__ void pm_lnbwd_row(const PmGeom& g, int Cn, long row, int lane, const void* __restrict__ dy, const void* __restrict__ xs,
+                                             const float* __restrict__ ln_w, const float* __restrict__ mu, const float* __restrict__ rstd,
+                                             void* __restrict__ dx, float (&sw)[NIT][8], float (&sb)[NIT][8]) {
   const int nch = Cn / 8;
   const long base = GATHER ? pm_base(g, row) : row * Cn;
   const float m = mu[row], rs = rstd[row];
@@ -283,6 +285,7 @@ __global__ __launch_bounds__(256) void pm_lnbwd_k(PmGeom g, int Cn, const void* 
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       xh[it][e] = (xh[it][e] - m) * rs;
+      if (SUMS) { sw[it][e] += dh[it][e] * xh[it][e]; sb[it][e] += dh[it][e]; }      // (a clamped chunk's sums are never flushed)
       dh[it][e] *= lw[e];
       if (c < nch) { s1 += dh[it][e]; s2 += dh[it][e] * xh[it][e]; }
     }
@@ -296,6 +299,134 @@ __global__ __launch_bounds__(256) void pm_lnbwd_k(PmGeom g, int Cn, const void* 
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = rs * (dh[it][e] - m1 - xh[it][e] * m2);
       pm_st16(dx, off[it], pm_pack(o));
+    }
+}
+
+template <bool GATHER, int NIT>
+__global__ __launch_bounds__(256) void pm_lnbwd_k(PmGeom g, int Cn, const void* __restrict__ dy, const void* __restrict__ xs,
+                                                  const float* __restrict__ ln_w, const float* __restrict__ mu, const float* __restrict__ rstd,
+                                                  void* __restrict__ dx) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= g.rows) return;                         // (no barrier in this kernel)
+  float none[NIT][8];
+  pm_lnbwd_row<GATHER, NIT, false>(g, Cn, row, lane, dy, xs, ln_w, mu, rstd, dx, none, none);
+}
+
+// ---- the same with the column sums of a trainable norm: d ln_w[c] = sum_r dy[r][c] x^[r][c], d ln_b[c] = sum_r dy[r][c] -----------------
+// A wavefront walks the rows wave, wave + 4 gridDim.x, ... and keeps both sums of its 8 NIT channels in registers; the grid is at most one
+// round of resident workgroups.  The four wavefronts combine by store / barrier / column-sum through LDS ([4][Cn] floats, one
+// quantity after the other), and the workgroup leaves with plain stores into its own partials part[wg][2][Cn], finished by part_reduce.
+constexpr int PM_SUMS_MAX_WG = 2048, PM_SUMS_ROWS_PER_WG = 32;
+static long pm_sums_max_wgs(long rows) {
+  const long n = (rows + PM_SUMS_ROWS_PER_WG - 1) / PM_SUMS_ROWS_PER_WG;
+  return n < PM_SUMS_MAX_WG ? n : PM_SUMS_MAX_WG;
+}
+template <bool GATHER, int NIT>
+__global__ __launch_bounds__(256) void pm_lnbwd_sums_k(PmGeom g, int Cn, const void* __restrict__ dy, const void* __restrict__ xs,
+                                                       const float* __restrict__ ln_w, const float* __restrict__ mu,
+                                                       const float* __restrict__ rstd, void* __restrict__ dx, float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) char pm_smem[];
+  float* red = reinterpret_cast<float*>(pm_smem);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nch = Cn / 8;
+  float sw[NIT][8], sb[NIT][8];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sw[it][e] = sb[it][e] = 0.f;
+  for (long row = (long)blockIdx.x * 4 + wv; row < g.rows; row += 4L * gridDim.x)
+    pm_lnbwd_row<GATHER, NIT, true>(g, Cn, row, lane, dy, xs, ln_w, mu, rstd, dx, sw, sb);
+  float* p = part + (long)blockIdx.x * 2 * Cn;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      if (lane + 64 * it < nch) {
+        const float(&a)[8] = q == 0 ? sw[it] : sb[it];
+        float* d = red + wv * Cn + (lane + 64 * it) * 8;
+        *reinterpret_cast<float4*>(d) = make_float4(a[0], a[1], a[2], a[3]);
+        *reinterpret_cast<float4*>(d + 4) = make_float4(a[4], a[5], a[6], a[7]);
+      }
+    __syncthreads();
+    for (int c = tid; c < Cn; c += 256) p[q * Cn + c] = (red[c] + red[Cn + c]) + (red[2 * Cn + c] + red[3 * Cn + c]);
+  }
+}
+
+// ---- weight gradient: dW [2C][4C] += D^T . A over a slab of rows ---------------------------------------------------------------------------
+// D [rows][2C] bf16 (dout for NORM_FIRST, dpre for NORM_LAST), A [rows][4C] = the operand the forward multiplied with W: the gathered row
+// (NORM_LAST) or bf16(x^ ln_w + ln_b) of it (NORM_FIRST: pm_fwd_k's expression re-evaluated from the saved mu / rstd -- nothing pins
+// the two kernels to the same fma contraction, so an element may differ from the forward's by one bf16 ulp).  A is staged from the token map
+// and exists in LDS only.  The rows are the contraction, so both LDS images are [64 rows][128] MN-major (transpose reads).  A workgroup
+// owns a 128 x 128 tile of dW (blockIdx.x: column tile fastest) and the slab blockIdx.y of `sps` 64-row steps; a wavefront owns 32 columns
+// of the tile and all four 32-row blocks (2C % 64 == 0: a block of the ragged last tile is wholly inside or outside).  fp32 atomicAdd
+// into dW: one contributor per slab, at most PM_WG_MAX_SLABS.
+constexpr int PM_WG_BR = 64, PM_WG_MAX_SLABS = 40;
+constexpr int PM_WG_LDS = 2 * PM_WG_BR * PM_P_MN;
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pm_wgrad_k(PmGeom g, int sps, const void* __restrict__ d, const void* __restrict__ x,
+                                                  const float* __restrict__ ln_w, const float* __restrict__ ln_b, const float* __restrict__ mu,
+                                                  const float* __restrict__ rstd, float* __restrict__ dw) {
+  extern __shared__ __attribute__((aligned(16))) char pm_smem[];
+  char* Dimg = pm_smem;
+  char* Aimg = pm_smem + PM_WG_BR * PM_P_MN;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int K = 4 * g.C, N = 2 * g.C;
+  const int kt = K / PM_BN;
+  const int n0 = ((int)blockIdx.x / kt) * PM_BN, k0 = ((int)blockIdx.x % kt) * PM_BN;
+  const int rows = (int)g.rows;
+  const int rbeg = (int)blockIdx.y * sps * PM_WG_BR;
+  const int rend = imin_d(rows, rbeg + sps * PM_WG_BR);
+  // this thread's chunk of every 16-row group of the A tile: channels k0 + ac .. + 7 of row tid / 16
+  const int ac = (tid & 15) * 8, ar = tid >> 4;
+  const int so = pm_seg(g, k0 + ac);
+  float lw[8], lb[8];
+  if (FIRST) { ldf<8>(ln_w, k0 + ac, lw); ldf<8>(ln_b, k0 + ac, lb); }
+  mt_f32x16 acc[PM_BN / 32];
+#pragma unroll
+  for (int i = 0; i < PM_BN / 32; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  for (int r0 = rbeg; r0 < rend; r0 += PM_WG_BR) {
+    uint4 raw[PM_WG_BR / 16];
+    float mean[PM_WG_BR / 16], rs[PM_WG_BR / 16];
+#pragma unroll
+    for (int it = 0; it < PM_WG_BR / 16; ++it) {
+      const int r = r0 + it * 16 + ar, rc = r < rows ? r : rows - 1;
+      raw[it] = pm_ld16(x, pm_base(g, rc) + so);
+      if (FIRST) { mean[it] = mu[rc]; rs[it] = rstd[rc]; }
+    }
+    __syncthreads();                                 // the previous step's images are consumed
+    stage_tile<DT_BF16, PM_WG_BR, PM_BN>(Dimg, PM_P_MN, d, N, r0, rows, n0, N, tid);
+#pragma unroll
+    for (int it = 0; it < PM_WG_BR / 16; ++it) {
+      const bool rv = r0 + it * 16 + ar < rows;
+      uint4 a = raw[it];
+      if (FIRST) {
+        float v[8], y[8];
+        unpack<DT_BF16, 8>(raw[it], v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = rv ? (v[e] - mean[it]) * rs[it] * lw[e] + lb[e] : 0.f;
+        a = pm_pack(y);
+      } else if (!rv) {
+        a = make_uint4(0, 0, 0, 0);
+      }
+      *reinterpret_cast<uint4*>(Aimg + (it * 16 + ar) * PM_P_MN + ac * 2) = a;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PM_BN / 32; ++i)
+      if (n0 + 32 * i < N)
+        mma_tile<DT_BF16, false, false>(acc[i], Dimg, PM_P_MN, 32 * i, Aimg, PM_P_MN, 32 * wv, PM_WG_BR, lane);
+  }
+  if (rbeg >= rend) return;
+#pragma unroll
+  for (int i = 0; i < PM_BN / 32; ++i)
+    if (n0 + 32 * i < N) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        unsafeAtomicAdd(dw + (long)(n0 + 32 * i + mt_row(r, lane)) * K + k0 + 32 * wv + (lane & 31), acc[i][r]);
     }
 }
 
@@ -332,6 +463,42 @@ static void pm_lnbwd(dim3 grid, hipStream_t s, const PmGeom& g, int Cn, const vo
   else hipLaunchKernelGGL((pm_lnbwd_k<GATHER, 3>), grid, dim3(256), 0, s, g, Cn, dy, xs, ln_w, mu, rstd, dx);
 }
 
+// the column-sum variant: at most one round of resident workgroups, each with at least PM_SUMS_ROWS_PER_WG rows where there are that many
+template <bool GATHER>
+static void pm_lnbwd_sums(hipStream_t s, const PmGeom& g, int Cn, const void* dy, const void* xs, const float* ln_w, const float* mu,
+                          const float* rstd, void* dx, float* part, float* dln_w, float* dln_b) {
+  const size_t shmem = (size_t)4 * Cn * sizeof(float);
+  auto go = [&](auto kern) {
+    long nwg = wg_capacity(reinterpret_cast<const void*>(kern), shmem);
+    const long most = pm_sums_max_wgs(g.rows);
+    if (nwg > most) nwg = most;
+    if (nwg < 1) nwg = 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), shmem, s, g, Cn, dy, xs, ln_w, mu, rstd, dx, part);
+    PartTable t;
+    t.NQ = 2; t.C = Cn;
+    t.d[0] = PartDesc{0, 1, (int)nwg, 1, dln_w, 0, 1.f};
+    t.d[1] = PartDesc{1, 1, (int)nwg, 1, dln_b, 0, 1.f};
+    part_reduce((void*)s, part, t, 2);
+  };
+  if (Cn <= 512) go(pm_lnbwd_sums_k<GATHER, 1>);
+  else if (Cn <= 1024) go(pm_lnbwd_sums_k<GATHER, 2>);
+  else go(pm_lnbwd_sums_k<GATHER, 3>);
+}
+
+template <bool FIRST>
+static void pm_wgrad(hipStream_t s, const PmGeom& g, const void* d, const void* x, const float* ln_w, const float* ln_b, const float* mu,
+                     const float* rstd, float* dw) {
+  const long steps = (g.rows + PM_WG_BR - 1) / PM_WG_BR;
+  const long sps = (steps + PM_WG_MAX_SLABS - 1) / PM_WG_MAX_SLABS;          // whole 64-row steps per slab
+  const long slabs = (steps + sps - 1) / sps;                                // <= PM_WG_MAX_SLABS, none empty
+  const int tiles = ((2 * g.C + PM_BN - 1) / PM_BN) * (4 * g.C / PM_BN);
+  hipLaunchKernelGGL((pm_wgrad_k<FIRST>), dim3((unsigned)tiles, (unsigned)slabs), dim3(256), (size_t)PM_WG_LDS, s, g, (int)sps, d, x, ln_w, ln_b,
+                     mu, rstd, dw);
+}
+
+static long pm_ws_rows_bytes(int mode, const PmGeom& g) { return g.rows * (mode == DGSCT_PMERGE_NORM_FIRST ? 4 : 2) * g.C * 2; }
+static long pm_part_offset(int mode, const PmGeom& g) { return (pm_ws_rows_bytes(mode, g) + 255) / 256 * 256; }
+
 }  // namespace dgsct
 
 using namespace dgsct;
@@ -342,7 +509,15 @@ int64_t dgsct_patch_merge_ws_bytes(int mode, int B, int H, int W, int C) {
   clear_error();
   PmGeom g;
   if (!pm_check("dgsct_patch_merge_ws_bytes", mode, B, H, W, C, g)) return -1;
-  return g.rows * (mode == DGSCT_PMERGE_NORM_FIRST ? 4 : 2) * C * 2;
+  return pm_ws_rows_bytes(mode, g);
+}
+
+int64_t dgsct_patch_merge_params_ws_bytes(int mode, int B, int H, int W, int C) {
+  clear_error();
+  PmGeom g;
+  if (!pm_check("dgsct_patch_merge_params_ws_bytes", mode, B, H, W, C, g)) return -1;
+  const long cn = (mode == DGSCT_PMERGE_NORM_FIRST ? 4 : 2) * C;
+  return pm_part_offset(mode, g) + pm_sums_max_wgs(g.rows) * 2 * cn * (long)sizeof(float);
 }
 
 int dgsct_patch_merge_forward(int mode, int B, int H, int W, int C, const void* x, const void* w_bf16, const float* ln_w, const float* ln_b,
@@ -392,6 +567,40 @@ int dgsct_patch_merge_backward(int mode, int B, int H, int W, int C, const void*
   } else {
     pm_lnbwd<false>(rgrid, s, g, 2 * C, dout, pre, ln_w, mu, rstd, ws);
     pm_launch(pm_dgemm_k<true>, ggrid, (size_t)PM_DG_LDS, s, g, (const void*)ws, w_bf16, dx);
+  }
+  check_async(who);
+  return has_error() ? 1 : 0;
+}
+
+int dgsct_patch_merge_backward_params(int mode, int B, int H, int W, int C, const void* dout, const void* x, const void* w_bf16,
+                                      const float* ln_w, const float* ln_b, const void* pre, const float* mu, const float* rstd, float eps,
+                                      void* dx, float* dw, float* dln_w, float* dln_b, void* ws, void* stream) {
+  clear_error();
+  const char* who = "dgsct_patch_merge_backward_params";
+  PmGeom g;
+  if (!pm_check(who, mode, B, H, W, C, g)) return 2;
+  if (!dout || !x || !w_bf16 || !ln_w || !ln_b || !mu || !rstd || !dx || !dw || !dln_w || !dln_b || !ws) { set_error("%s: NULL argument", who); return 2; }
+  if (mode == DGSCT_PMERGE_NORM_LAST && !pre) { set_error("%s: NORM_LAST needs `pre` as well as `x`", who); return 2; }
+  (void)eps;                                          // rstd already carries it
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 ggrid((unsigned)((g.rows + PM_DG_BM - 1) / PM_DG_BM), (unsigned)(4 * C / PM_BN));
+  const int cn = (mode == DGSCT_PMERGE_NORM_FIRST ? 4 : 2) * C;
+  float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + pm_part_offset(mode, g));
+  clear_async();
+  if (hipMemsetAsync(dw, 0, (size_t)8 * C * C * sizeof(float), s) != hipSuccess || hipMemsetAsync(dln_w, 0, (size_t)cn * sizeof(float), s) != hipSuccess ||
+      hipMemsetAsync(dln_b, 0, (size_t)cn * sizeof(float), s) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: hipMemsetAsync of the gradient buffers failed", who);
+    return 1;
+  }
+  if (mode == DGSCT_PMERGE_NORM_FIRST) {
+    pm_launch(pm_dgemm_k<false>, ggrid, (size_t)PM_DG_LDS, s, g, dout, w_bf16, ws);
+    pm_lnbwd_sums<true>(s, g, cn, (const void*)ws, x, ln_w, mu, rstd, dx, part, dln_w, dln_b);
+    pm_wgrad<true>(s, g, dout, x, ln_w, ln_b, mu, rstd, dw);
+  } else {
+    pm_lnbwd_sums<false>(s, g, cn, dout, pre, ln_w, mu, rstd, ws, part, dln_w, dln_b);
+    pm_launch(pm_dgemm_k<true>, ggrid, (size_t)PM_DG_LDS, s, g, (const void*)ws, w_bf16, dx);
+    pm_wgrad<false>(s, g, (const void*)ws, x, ln_w, ln_b, mu, rstd, dw);
   }
   check_async(who);
   return has_error() ? 1 : 0;

@@ -11,12 +11,20 @@ four stages so that a loss on the last stage's output trains the adapters of the
 
 The HIP path (csrc/pmerge.hip: one launch forward for HTS-AT, two for Swin-V2, two backward, the [rows, 4 dim] concatenation never written
 by a forward) takes bf16 GPU maps inside the kernel's limits -- H, W even, dim a multiple of 32, 4 dim <= 1536 (HTS-AT) / 2 dim <= 1536
-(Swin-V2).  ``fused=True`` selects it and raises on anything it does not take (a trainable parameter included); ``fused=False`` is the
+(Swin-V2).  ``fused=True`` selects it and raises on anything it does not take (a trainable parameter without ``weight_grads=True`` included); ``fused=False`` is the
 ATen formulation (the one pinned to the reference on the CPU); ``fused=None`` takes the kernels only at the shapes where they have been
 measured faster than ATen in both directions (``_KERNELS_FASTER``, from profiles/patch_merging_bench.txt: seven of the nine merges of
 the AVE trunk at the Swin-V2-B / -L widths; the two widest last merges lose their forward and stay ATen) and ATen at every other shape,
-unmeasured ones included; ``fused=True`` is the opt-in to the kernels anywhere inside the limits.  **The fused path returns
-no weight gradients**: under ``fused=None`` a merge with a parameter that requires grad (AVS-S4 trains HTS-AT) takes the ATen formulation.
+unmeasured ones included; ``fused=True`` is the opt-in to the kernels anywhere inside the limits.
+
+A merge with a parameter that requires grad (AVS-S4 trains HTS-AT): **the kernels return weight gradients only on request**,
+``weight_grads=True``.  Without the keyword such a merge takes the ATen formulation under ``fused=None`` and raises under ``fused=True``,
+as before.  With it, ``fused=True`` runs the kernels with ``dgsct_patch_merge_backward_params`` as the backward (dx bit for bit the frozen
+path's, plus ``reduction.weight`` / ``norm.weight`` / ``norm.bias`` gradients accumulated in fp32 and returned in each parameter's dtype:
+fp32 masters get fp32 gradients) and raises when the library lacks that export; ``fused=None`` takes them only at the shapes of
+``_KERNELS_FASTER_TRAIN`` (profiles/patch_merging_train_bench.txt: the first two HTS-AT merges) and ATen elsewhere; ``fused=False`` is ATen.  The Swin-V2 form then
+keeps the stage map alive until backward as well as the product before the norm (the weight gradient re-gathers its operand).  A frozen
+merge is unaffected by the keyword.
 
 Parity: ``HTSATPatchMerging`` is pinned against the reference class and ``SwinV2PatchMerging`` against Hugging Face transformers'
 ``Swinv2PatchMerging`` (tools/make_golden_patch_merging.py -> tests/golden/ref_patch_merging.pt); **parity against timm itself stays
@@ -44,6 +52,13 @@ _KERNELS_FASTER: frozenset = frozenset({
     (ops.PMERGE_NORM_LAST, 2304, 192), (ops.PMERGE_NORM_LAST, 576, 384),                                            # Swin-V2-L stages 0, 1
 })
 
+# The same for a TRAINABLE merge with weight_grads=True (forward + backward with parameter gradients together): the shapes at which
+# `tools/patch_merging_bench.py --train` measured the kernels' slowest window faster than the fastest window of the formulation
+# AVETrunk(train_htsat=True) runs without the keyword (fp32 masters through ATen); profiles/patch_merging_train_bench.txt, BT = 160:
+# 411 against 1822 us and 302 against 778 us.  The last audio merge (256 tokens x 384: 469 against 476 us, the windows overlap, the
+# forward alone loses) is NOT listed and stays ATen under fused=None.
+_KERNELS_FASTER_TRAIN: frozenset = frozenset({(ops.PMERGE_NORM_FIRST, 4096, 96), (ops.PMERGE_NORM_FIRST, 1024, 192)})
+
 
 def gather_2x2(x: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """[B, H*W, C] -> [B, (H/2)(W/2), 4C]: the reference's four strided slices and their cat (== view(B,H/2,2,W/2,2,C).permute(0,1,3,4,2,5))"""
@@ -57,10 +72,10 @@ class _PatchMerging(nn.Module):
     _MODE = -1
     _NORM_MULT = 0
 
-    def __init__(self, input_resolution: Tuple[int, int], dim: int, fused: Optional[bool] = None, lib=None):
+    def __init__(self, input_resolution: Tuple[int, int], dim: int, fused: Optional[bool] = None, lib=None, weight_grads: bool = False):
         super().__init__()
         self.input_resolution, self.dim = tuple(input_resolution), dim
-        self.fused, self._lib = fused, lib
+        self.fused, self._lib, self.weight_grads = fused, lib, bool(weight_grads)
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
         self.norm = nn.LayerNorm(self._NORM_MULT * dim)
 
@@ -75,23 +90,45 @@ class _PatchMerging(nn.Module):
                                                       ps[2].detach().float().contiguous())
         return c[1:]
 
-    def _use_fused(self, x: torch.Tensor) -> bool:
-        if self.fused is False:
-            return False
+    def _supported(self, x: torch.Tensor) -> bool:
+        """the kernels take x; ``fused=True`` raises where they do not"""
         H, W = self.input_resolution
         ok = ops.patch_merge_supported(x, H, W, self._MODE) and x.device == self.reduction.weight.device
         if self.fused and not ok:
             raise RuntimeError(f"dg-sct_amd: {type(self).__name__}(fused=True) takes bf16 CUDA/HIP maps with dim a multiple of 32 and "
                                f"{self._NORM_MULT} dim <= 1536 (got {tuple(x.shape)} {x.dtype} on "
                                f"{x.device}; fused=False is the ATen formulation)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.fused:
-                raise RuntimeError(f"dg-sct_amd: {type(self).__name__}(fused=True): a parameter requires grad and the kernels return the input "
-                                   f"gradient only (freeze the module, or fused=None / False for the ATen formulation)")
-            return False                                   # the kernels return dx only
+        return ok
+
+    def _use_fused(self, x: torch.Tensor) -> bool:
+        """a FROZEN merge (no parameter requires grad, or grad mode is off)"""
+        if self.fused is False:
+            return False
+        H, W = self.input_resolution
         if self.fused is None and (self._MODE, H * W, self.dim) not in _KERNELS_FASTER:
             return False
-        return ok
+        return self._supported(x)
+
+    def _use_fused_train(self, x: torch.Tensor) -> bool:
+        """a TRAINABLE merge: the kernels only with ``weight_grads=True``, and under ``fused=None`` only at the measured shapes"""
+        if self.fused is False:
+            return False
+        H, W = self.input_resolution
+        if not self.weight_grads:
+            if self.fused and self._supported(x):
+                raise RuntimeError(f"dg-sct_amd: {type(self).__name__}(fused=True): a parameter requires grad and without weight_grads=True "
+                                   f"the kernels return the input gradient only (pass weight_grads=True, freeze the module, or "
+                                   f"fused=None / False for the ATen formulation)")
+            return False                                   # dx only without the keyword
+        if self.fused is None and (self._MODE, H * W, self.dim) not in _KERNELS_FASTER_TRAIN:
+            return False
+        lib = self._lib or ops._lib.default_lib()
+        if not lib.has_patch_merge_params():
+            if self.fused:
+                raise RuntimeError(f"dg-sct_amd: {type(self).__name__}(fused=True, weight_grads=True): {lib.path} does not export "
+                                   f"dgsct_patch_merge_backward_params (fused=None / False for the ATen formulation)")
+            return False
+        return self._supported(x)
 
     def _aten(self, g: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
@@ -102,7 +139,11 @@ class _PatchMerging(nn.Module):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
         assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
-        if self._use_fused(x):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self._use_fused_train(x):
+                return ops._patch_merge_train(x, self.reduction.weight, self.norm.weight, self.norm.bias, self.norm.eps, H, W, self._MODE,
+                                              self._lib, self._cached())
+        elif self._use_fused(x):
             w, ln_w, ln_b = self._cached()
             return ops.patch_merge(x, w, ln_w, ln_b, self.norm.eps, H, W, self._MODE, self._lib)
         return self._aten(gather_2x2(x, H, W))
@@ -113,7 +154,8 @@ class _PatchMerging(nn.Module):
 
 class HTSATPatchMerging(_PatchMerging):
     """``PatchMerging`` of htsat.py:259-295: ``reduction(norm(cat(x0, x1, x2, x3)))`` with ``norm = LayerNorm(4 dim)``.  Fused: one launch
-    forward (csrc/pmerge.hip, DGSCT_PMERGE_NORM_FIRST), two backward, dx only -- with a trainable parameter fused=None is ATen, fused=True raises."""
+    forward (csrc/pmerge.hip, DGSCT_PMERGE_NORM_FIRST), two backward, dx only -- with a trainable parameter fused=None is ATen and fused=True
+    raises, unless ``weight_grads=True`` asks for the backward that also returns the three parameter gradients (module docstring)."""
     _MODE = ops.PMERGE_NORM_FIRST
     _NORM_MULT = 4
 
@@ -124,7 +166,8 @@ class HTSATPatchMerging(_PatchMerging):
 class SwinV2PatchMerging(_PatchMerging):
     """timm 0.6.12 ``swin_transformer_v2.PatchMerging`` as the AVE loop calls it: ``norm(reduction(cat(x0, x1, x2, x3)))`` with
     ``norm = LayerNorm(2 dim)``.  Fused: two launches each way (DGSCT_PMERGE_NORM_LAST), dx only -- with a trainable parameter fused=None is
-    ATen, fused=True raises.  Parity against timm unpinned (see the module docstring)."""
+    ATen and fused=True raises, unless ``weight_grads=True`` (which keeps the input map alive until backward as well as the product before
+    the norm).  Parity against timm unpinned (see the module docstring)."""
     _MODE = ops.PMERGE_NORM_LAST
     _NORM_MULT = 2
 
@@ -161,12 +204,13 @@ class AVETrunk(nn.Module):
     ``(pooled_v [BT, 1, Cv_last], pooled_a [BT, 1, Ca_last], outs, maps)``: outs[s] = (f_v, f_a) leaving stage s (before its merge and before
     ``norm``), maps = (map_v, map_a) of the last p2 adapters.  Sub-modules: ``stack`` (the adapters, the only trainable part), ``blocks``
     (FrozenBlocks), ``vis_merge`` / ``aud_merge`` (one per stage boundary, frozen like the blocks; ``train_htsat=True`` keeps the audio
-    merges fp32 and trainable, which sends them down the ATen formulation), ``norm``.  ``stack_kw`` goes to AdapterStack (``lib=``,
+    merges fp32 masters and trainable, which sends them down the ATen formulation unless ``merge_weight_grads=True`` hands them
+    ``weight_grads=True``: see the module docstring; the Swin-V2 merges are frozen in every reference task and never get it), ``norm``.  ``stack_kw`` goes to AdapterStack (``lib=``,
     ``concurrent=``, ...).  Consecutive stages must quarter the tokens and double the width.  CPU tensors are taken only with ``lib=`` (the
     host emulation of the adapter kernels): that path exists for the tests."""
 
     def __init__(self, stages: Sequence[Dict[str, int]], opt=None, dtype: torch.dtype = torch.bfloat16, fused: Optional[bool] = None,
-                 train_htsat: bool = False, **stack_kw):
+                 train_htsat: bool = False, merge_weight_grads: bool = False, **stack_kw):
         super().__init__()
         stages = [dict(s) for s in stages]
         for s, (a, b) in enumerate(zip(stages[:-1], stages[1:])):
@@ -184,7 +228,8 @@ class AVETrunk(nn.Module):
         self.blocks = FrozenBlocks(stages, dtype=dtype, fused=fused, train_htsat=train_htsat)
         side = lambda n: int(round(math.sqrt(n)))             # noqa: E731
         self.vis_merge = nn.ModuleList([SwinV2PatchMerging((side(s["Nv"]),) * 2, s["Cv"], fused=fused, lib=self._lib) for s in stages[:-1]])
-        self.aud_merge = nn.ModuleList([HTSATPatchMerging((side(s["Na"]),) * 2, s["Ca"], fused=fused, lib=self._lib) for s in stages[:-1]])
+        self.aud_merge = nn.ModuleList([HTSATPatchMerging((side(s["Na"]),) * 2, s["Ca"], fused=fused, lib=self._lib, weight_grads=merge_weight_grads)
+                                        for s in stages[:-1]])
         self.norm = nn.LayerNorm(stages[-1]["Cv"])
         self.vis_merge.to(dtype)
         self.norm.to(dtype)

@@ -964,7 +964,7 @@ def patch_merge_supported(x: torch.Tensor, H: int, W: int, mode: int) -> bool:
 
 
 class _PatchMergeFn(torch.autograd.Function):
-    """one library call each way (dgsct_patch_merge_*); gradient for x only: the merges are frozen"""
+    """one library call each way (dgsct_patch_merge_*); gradient for x only: a frozen merge (_PatchMergeTrainFn is the trainable one)"""
 
     @staticmethod
     def forward(ctx, lib, x, w, ln_w, ln_b, eps, H, W, mode):
@@ -1025,3 +1025,83 @@ def patch_merge(x: torch.Tensor, w_bf16: torch.Tensor, ln_w: torch.Tensor, ln_b:
     if any(t.requires_grad for t in (w_bf16, ln_w, ln_b)):
         raise RuntimeError(f"dg-sct_amd: {who} returns no weight gradients: pass detached w_bf16 / ln_w / ln_b (a trainable merge takes the ATen formulation)")
     return _PatchMergeFn.apply(lib or _lib.default_lib(), x.contiguous(), w_bf16, ln_w, ln_b, float(eps), int(H), int(W), int(mode))
+
+
+class _PatchMergeTrainFn(torch.autograd.Function):
+    """_PatchMergeFn for a trainable merge: the parameters are inputs, and backward is dgsct_patch_merge_backward_params"""
+
+    @staticmethod
+    def forward(ctx, lib, x, weight, ln_weight, ln_bias, w, ln_w, ln_b, eps, H, W, mode):
+        B, L, C_ = x.shape
+        rows = B * (H // 2) * (W // 2)
+        out = torch.empty(B, rows // B, 2 * C_, dtype=x.dtype, device=x.device)
+        pre = torch.empty_like(out) if mode == PMERGE_NORM_LAST else None
+        mu = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _mark_stream_use(x, w, ln_w, ln_b)
+        with _dev_guard(x):
+            lib.patch_merge_forward(mode, B, H, W, C_, x.data_ptr(), w.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps), out.data_ptr(),
+                                    pre.data_ptr() if pre is not None else None, mu.data_ptr(), rstd.data_ptr(), _stream_of(x))
+        ctx.lib, ctx.geom, ctx.eps = lib, (mode, B, H, W, C_), float(eps)
+        ctx.param_dtypes = (weight.dtype, ln_weight.dtype, ln_bias.dtype)
+        # the weight gradient needs the operand the forward multiplied with W, which is re-made from x in both modes: NORM_LAST keeps
+        # the stage map alive as well as `pre`
+        ctx.save_for_backward(x, w, ln_w, ln_b, mu, rstd, *(() if pre is None else (pre,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, ln_w, ln_b, mu, rstd = ctx.saved_tensors[:6]
+        pre = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        mode, B, H, W, C_ = ctx.geom
+        dout = dout.contiguous()
+        if dout.dtype != x.dtype:
+            dout = dout.to(x.dtype)
+        dx = torch.empty(B, H * W, C_, dtype=x.dtype, device=x.device)
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dw, dln_w, dln_b = torch.empty(2 * C_, 4 * C_, **f32), torch.empty_like(ln_w), torch.empty_like(ln_b)      # (zeroed by the call)
+        ws = torch.empty(ctx.lib.patch_merge_params_ws_bytes(*ctx.geom), dtype=torch.uint8, device=x.device)
+        _mark_stream_use(x, w, ln_w, ln_b, mu, rstd, dout, pre)
+        with _dev_guard(x):
+            ctx.lib.patch_merge_backward_params(*ctx.geom, dout.data_ptr(), x.data_ptr(), w.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+                                                pre.data_ptr() if pre is not None else None, mu.data_ptr(), rstd.data_ptr(), ctx.eps,
+                                                dx.data_ptr(), dw.data_ptr(), dln_w.data_ptr(), dln_b.data_ptr(), ws.data_ptr(), _stream_of(x))
+        need = ctx.needs_input_grad
+        grads = [g.to(dt) if n else None for g, dt, n in zip((dw, dln_w, dln_b), ctx.param_dtypes, need[2:5])]
+        return (None, dx if need[1] else None, *grads, None, None, None, None, None, None, None)
+
+
+def patch_merge_train(x: torch.Tensor, weight: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float, H: int, W: int, mode: int,
+                      lib: Optional[Lib] = None) -> torch.Tensor:
+    """`patch_merge` for a TRAINABLE merge: `weight` [2C, 4C], `ln_w`, `ln_b` ([4C] NORM_FIRST / [2C] NORM_LAST) are the parameters
+    themselves, in any floating dtype (fp32 masters or bf16), and receive gradients.  The forward runs the same kernels on a bf16 copy of
+    the weight and fp32 copies of the norm vectors; backward is
+    dgsct_patch_merge_backward_params: dx bit for bit as `patch_merge` returns it, and dW / d ln_w / d ln_b accumulated in fp32 and cast
+    to each parameter's dtype (fp32 masters get fp32 gradients).  NORM_LAST saves x as well as the product before the norm: the weight
+    gradient re-gathers its operand from x, so the stage map stays alive until backward (the frozen `patch_merge` keeps only `pre`)."""
+    return _patch_merge_train(x, weight, ln_w, ln_b, eps, H, W, mode, lib)
+
+
+def _patch_merge_train(x, weight, ln_w, ln_b, eps, H, W, mode, lib=None, cached=None):
+    """`patch_merge_train`; `cached` = (weight in bf16, ln_w, ln_b in fp32) where the caller keeps those copies, as the merge modules do"""
+    who = "patch_merge_train"
+    if mode not in (PMERGE_NORM_FIRST, PMERGE_NORM_LAST):
+        raise RuntimeError(f"dg-sct_amd: {who}: unknown mode {mode}")
+    if not patch_merge_supported(x, H, W, mode):
+        raise RuntimeError(f"dg-sct_amd: {who} takes a bf16 CUDA/HIP map [B, H*W, C] with H, W even, C a multiple of 32 and "
+                           f"{'4C' if mode == PMERGE_NORM_FIRST else '2C'} <= 1536 (got {tuple(getattr(x, 'shape', ()))} "
+                           f"{getattr(x, 'dtype', None)}, map {H} x {W}; no CPU kernels: fused=False is the ATen formulation)")
+    lib = lib or _lib.default_lib()
+    if not lib.has_patch_merge_params():
+        raise RuntimeError(f"dg-sct_amd: {who}: {lib.path} does not export dgsct_patch_merge_backward_params (a library without the merge's "
+                           f"parameter gradients; the ATen formulation trains a merge without it)")
+    C_ = x.shape[-1]
+    dev = x.device
+    cn = 4 * C_ if mode == PMERGE_NORM_FIRST else 2 * C_
+    for name, t, shape in (("weight", weight, (2 * C_, 4 * C_)), ("ln_w", ln_w, (cn,)), ("ln_b", ln_b, (cn,))):
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point() or tuple(t.shape) != shape or t.device != dev:
+            raise RuntimeError(f"dg-sct_amd: {who}: {name} must be a floating-point tensor {list(shape)} on {dev}")
+    if cached is None:
+        with torch.no_grad():
+            cached = (weight.detach().to(torch.bfloat16).contiguous(), ln_w.detach().float().contiguous(), ln_b.detach().float().contiguous())
+    return _PatchMergeTrainFn.apply(lib, x.contiguous(), weight, ln_w, ln_b, *cached, float(eps), int(H), int(W), int(mode))

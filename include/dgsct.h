@@ -298,10 +298,14 @@ int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int 
  *   DGSCT_PMERGE_NORM_LAST (Swin-V2, timm 0.6.12 PatchMerging): out = LN_2C(row . w^T); ln_w / ln_b fp32 [2C]; two launches; `pre`
  *     [rows][2C] bf16 receives the product before the norm (kept for backward), mu / rstd its row statistics.
  *   out [B][(H/2)(W/2)][2C] bf16.  The same rounding points as LayerNorm and Linear in bf16, one after the other.
- * backward: dx [B][H*W][C] bf16 only (the merges are frozen: no parameter gradients), every element written exactly once, two launches;
+ * backward: dx [B][H*W][C] bf16 only (a frozen merge: no parameter gradients), every element written exactly once, two launches;
  *   ws: dgsct_patch_merge_ws_bytes(...) bytes of scratch.  NORM_FIRST reads x (pre NULL), NORM_LAST reads pre (x may be NULL).
+ * backward_params (a trainable merge): dx exactly as dgsct_patch_merge_backward computes it (bit for bit), plus the parameter gradients
+ *   in fp32: dw [2C][4C], dln_w / dln_b [4C] (NORM_FIRST) | [2C] (NORM_LAST).  The call zeroes dw / dln_w / dln_b on `stream` itself
+ *   (dw is summed with fp32 atomics over at most 40 row slabs: its last bits depend on their arrival order).  NORM_FIRST needs x;
+ *   NORM_LAST needs x AND pre.  ws: dgsct_patch_merge_params_ws_bytes(...) bytes (the scratch above + per-workgroup column sums).
  * Limits: H, W even and >= 2; C a multiple of 32, >= 32; 4C <= 1536 (NORM_FIRST), 2C <= 1536 (NORM_LAST); bf16 only.
- * Asynchronous on `stream`; 0 or an error code (dgsct_patch_merge_ws_bytes: -1). */
+ * Asynchronous on `stream`; 0 or an error code (dgsct_patch_merge_ws_bytes / _params_ws_bytes: -1). */
 #define DGSCT_PMERGE_NORM_FIRST 0
 #define DGSCT_PMERGE_NORM_LAST  1
 int64_t dgsct_patch_merge_ws_bytes(int mode, int B, int H, int W, int C);
@@ -309,6 +313,10 @@ int dgsct_patch_merge_forward(int mode, int B, int H, int W, int C, const void* 
                               float eps, void* out, void* pre /* NORM_LAST only, else NULL */, float* mu, float* rstd, void* stream);
 int dgsct_patch_merge_backward(int mode, int B, int H, int W, int C, const void* dout, const void* x, const void* w_bf16, const float* ln_w,
                                const void* pre, const float* mu, const float* rstd, float eps, void* dx, void* ws, void* stream);
+int64_t dgsct_patch_merge_params_ws_bytes(int mode, int B, int H, int W, int C);
+int dgsct_patch_merge_backward_params(int mode, int B, int H, int W, int C, const void* dout, const void* x, const void* w_bf16,
+                                      const float* ln_w, const float* ln_b, const void* pre, const float* mu, const float* rstd, float eps,
+                                      void* dx, float* dw /* [2C][4C] */, float* dln_w, float* dln_b /* [4C] | [2C] */, void* ws, void* stream);
 
 /* ---- gate application of the post-backbone TemporalAttention ---------------------------
  * Replaces the tail of `TemporalAttention.forward` (DG-SCT/AVE/nets/net_trans.py:240-251; AVVP nets/mgn.py:148-159):
