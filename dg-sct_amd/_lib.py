@@ -112,6 +112,8 @@ class Lib:
         c.dgsct_saved_region.argtypes = [C.POINTER(AdapterDesc), C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64)]
         c.dgsct_test_gemm.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
+        c.dgsct_test_tune.argtypes = [C.c_char_p, C.c_int]
+        c.dgsct_test_tune.restype = C.c_int
         c.dgsct_test_attn.argtypes = [C.c_int, C.POINTER(AttnArgs), C.c_void_p]
         c.dgsct_test_gemm_fp8.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
         c.dgsct_temporal_gate_forward.argtypes = [C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 14
@@ -355,8 +357,6 @@ class Lib:
         self._check(self.c.dgsct_test_attn(int(op), C.byref(args), stream), "dgsct_test_attn")
 
     def test_tune(self, key: str, value: int) -> int:
-        self.c.dgsct_test_tune.argtypes = [C.c_char_p, C.c_int]
-        self.c.dgsct_test_tune.restype = C.c_int
         return int(self.c.dgsct_test_tune(key.encode(), int(value)))
 
     def test_gemm(self, args: GemmArgs, stream: int):

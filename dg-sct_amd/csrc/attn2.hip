@@ -15,7 +15,6 @@
 //   TF [C/32][2][2][32][8]     : element (((j*2 + kk)*2 + h)*32 + c)*8 + e    = hi of tok[16 kk + 4 h + (e&3) + 8 (e>>2)][32 j + c]
 // (TF's latent-token order is the order in which a lane holds the probabilities of its token row after the first product).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "mma_tile.h"
@@ -899,13 +898,12 @@ __global__ __launch_bounds__(256) void tokattn_bwd3_k(const TB2Args p) {
 namespace {
 // one wave per row block leaves the SIMDs under-filled below ~2 waves each: let a workgroup split the channels instead
 bool csplit_ok(int B, int N, int C, int max_spw) {
-  static const bool off = getenv("DGSCT_ATTN_NOCSPLIT") != nullptr;
-  static const int min_c = getenv("DGSCT_ATTN_CSPLIT_MINC") ? atoi(getenv("DGSCT_ATTN_CSPLIT_MINC")) : 512;
+  constexpr int min_c = 512;
   const long blocks = (long)B * ((N + 31) / 32);
   const int spw = ((C + CS2 - 1) / CS2 + 3) / 4;
   // measured (tools/attn_bench.py, B = 160): wins where the per-wave slab chain is long (C >= 768: xattn_fwd 47.9 -> 33.0 us,
   // xattn_bwd 117 -> 79 us at N = 36, C = 1024), even at C = 512, loses at C = 384 (3 slabs: one wave of four idle)
-  return !off && blocks <= 1024 && C >= min_c && spw <= max_spw;
+  return blocks <= 1024 && C >= min_c && spw <= max_spw;
 }
 }  // namespace
 
@@ -922,9 +920,9 @@ static bool xattn_fwd3_launch(const Ctx& ctx, const XF2Args& a, int B) {
   return true;
 }
 static bool xattn_bwd3_launch(const Ctx& ctx, XB2Args a, int B) {
-  // round 6 (tools/attn_bench.py, DGSCT_ATTN_CSPLIT_MINC sweep): at C = 512 the wave-per-block kernel is the faster BACKWARD (N = 144:
+  // round 6 (tools/attn_bench.py, sweep of csplit_ok's min_c): at C = 512 the wave-per-block kernel is the faster BACKWARD (N = 144:
   // 58.3 vs 70.3 us) while the C-split FORWARD still wins there (20.5 vs 24.9 us): the backward splits from C >= 768 only
-  static const int min_c_bwd = getenv("DGSCT_XBWD_CSPLIT_MINC") ? atoi(getenv("DGSCT_XBWD_CSPLIT_MINC")) : 768;
+  constexpr int min_c_bwd = 768;
   if (a.C < min_c_bwd) return false;
   if (!csplit_ok(B, a.N, a.C, 2)) return false;          // X and dX1 slabs in registers: 64 VGPRs per slab pair
   const int spw = ((a.C + CS2 - 1) / CS2 + 3) / 4;
@@ -945,7 +943,7 @@ static bool tokattn_bwd3_launch(const Ctx& ctx, TB2Args a, int B) {
 // d my_tokens (one contribution per 32-row block: 25 of its 89 us at N = 144, C = 512, measured by switching them off) -- it
 // wins only where the slab chain is long: 126 -> 105 us at N = 36, C = 1024; 99 -> 94 at N = 64, C = 768
 bool tokattn_bwd_csplit(int B, int N, int C) {
-  static const int min_c = getenv("DGSCT_TOKBWD_CSPLIT_MINC") ? atoi(getenv("DGSCT_TOKBWD_CSPLIT_MINC")) : 768;
+  constexpr int min_c = 768;
   return C >= min_c && csplit_ok(B, N, C, 3);
 }
 

@@ -10,6 +10,7 @@
 #include "plan.h"
 #include "prims.h"
 #include "gemm_int.h"
+#include "tune.h"
 
 using namespace dgsct;
 
@@ -354,27 +355,11 @@ static bool whatif_allowed(int value) {
 }
 
 int dgsct_test_tune(const char* key, int value) {
-  if (key && (!strcmp(key, "skip") || !strcmp(key, "noatomic") || !strcmp(key, "skipmaxc") || !strcmp(key, "skipminc")) && !whatif_allowed(value)) return -2;
-  if (key && !strcmp(key, "gemm8")) return gemm8_mode(value);
-  if (key && !strcmp(key, "skip")) return dgsct::plan_skip_mode(value);            // what-if timing switches (plan.cpp): results are garbage
-  if (key && !strcmp(key, "gemmfx")) return gemmfx_mode(value);
-  if (key && !strcmp(key, "g8stag")) return dgsct::gemm8_stag_mode(value);
-  if (key && !strcmp(key, "wgbt")) return dgsct::wgrad_bt_mode(value);
-  if (key && !strcmp(key, "noatomic")) return dgsct::gemm_noatomic_mode(value);
-  if (key && !strcmp(key, "skipmaxc")) return dgsct::plan_skip_maxc(value);
-  if (key && !strcmp(key, "skipminc")) return dgsct::plan_skip_minc(value);
-  if (key && !strcmp(key, "skinny")) return gemm_skinny_mode(value);
-  if (key && !strcmp(key, "gemmtall")) return gemm_tall_mode(value);
-  if (key && !strcmp(key, "rowfuse")) return rowfuse_mode(value);
-  if (key && !strcmp(key, "gatefuse")) return gatefuse_mode(value);
-  if (key && !strcmp(key, "bnfold")) return bnfold_mode(value);
-  if (key && !strcmp(key, "skfuse")) return skfuse_mode(value);
-  if (key && !strcmp(key, "vq1fuse")) return vq1fuse_mode(value);
-  if (key && !strcmp(key, "callprof")) {
-    if (value == 2) { call_prof_dump(getenv("DGSCT_CALL_PROF") ? getenv("DGSCT_CALL_PROF") : "/tmp/dgsct_callprof.txt"); return 0; }
-    return call_prof_mode(value);
-  }
-  return -1;
+  const int id = tune_find(key);
+  if (id < 0) return -1;
+  if (tune_is_whatif((TuneId)id) && !whatif_allowed(value)) return -2;
+  if (id == T_CALLPROF && value == 2) { call_prof_dump(getenv("DGSCT_CALL_PROF") ? getenv("DGSCT_CALL_PROF") : "/tmp/dgsct_callprof.txt"); return 0; }
+  return tune_set((TuneId)id, value);
 }
 
 int dgsct_prof_enable(int on) { gemm_prof_enable(on); return 0; }

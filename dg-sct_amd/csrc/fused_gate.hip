@@ -20,8 +20,6 @@
 // workgroup works on one frame and builds bf16(Wv2 (1 + ch_b)) (from the fp32 master) in LDS once; the grouped down-projection
 // is a block-diagonal [32 x C] image.  No __syncthreads in the token loop.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "mma_tile.h"
@@ -1015,19 +1013,9 @@ __global__ __launch_bounds__(256) void vq1_bwd_k(const VB p) {
   }   // items
   if (tid < C) p.part[(long)blockIdx.x * C + tid] = keep;
 }
-
-std::atomic<int> g_vq1fuse{-1};
-std::atomic<int> g_gatefuse{-1};
 }  // namespace
-
-int vq1fuse_mode(int set) {
-  if (g_vq1fuse.load(std::memory_order_relaxed) < 0) g_vq1fuse.store(getenv("DGSCT_NO_VQ1FUSE") ? 0 : 1, std::memory_order_relaxed);
-  const int old = g_vq1fuse.load(std::memory_order_relaxed);
-  if (set >= 0) g_vq1fuse.store(set > 2 ? 1 : set, std::memory_order_relaxed);      // 2: fused, and the forward also stores vq1 (tests)
-  return old;
-}
 bool vq1_fused_shape(int mode, int N, int C) { return mode == DT_BF16 && (C == 96 || C == 128) && N >= 32 && N % 32 == 0; }
-bool vq1_fused_supported(int mode, int N, int C) { return vq1fuse_mode(-1) && vq1_fused_shape(mode, N, C); }
+bool vq1_fused_supported(int mode, int N, int C) { return tune(T_VQ1FUSE) && vq1_fused_shape(mode, N, C); }
 static int vq1_wpf(const void* kern, int B, int N) {
   int cap = wg_capacity(kern, 0);
   int wpf = cap / B;
@@ -1071,12 +1059,6 @@ void vq1_bwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, 
 }
 
 
-int gatefuse_mode(int set) {
-  if (g_gatefuse.load(std::memory_order_relaxed) < 0) g_gatefuse.store(getenv("DGSCT_NO_GATEFUSE") ? 0 : 1, std::memory_order_relaxed);
-  const int old = g_gatefuse.load(std::memory_order_relaxed);
-  if (set >= 0) g_gatefuse.store(set > 2 ? 1 : set, std::memory_order_relaxed);
-  return old;
-}
 
 static bool gate_shape_ok(int mode, int N, int C, int ds, int g) {
   if (mode != DT_BF16) return false;
@@ -1084,7 +1066,7 @@ static bool gate_shape_ok(int mode, int N, int C, int ds, int g) {
   if (N % 32 || N < 32 || g < 1 || ds < 4 || ds > 32 || ds % 4 || ds % g || C % g) return false;
   return true;
 }
-bool gate_fused_supported(int mode, int N, int C, int ds, int g) { return gatefuse_mode(-1) && gate_shape_ok(mode, N, C, ds, g); }
+bool gate_fused_supported(int mode, int N, int C, int ds, int g) { return tune(T_GATEFUSE) && gate_shape_ok(mode, N, C, ds, g); }
 bool gate_bwd_fused_shape(int mode, int N, int C, int ds, int g) {
   return gate_shape_ok(mode, N, C, ds, g) && (C == 96 || C == 128) && ds == C / 8;
 }
@@ -1116,7 +1098,7 @@ void gatemod_fwd(const Ctx& ctx, const void* X1, const float* ch, const void* aq
 
 
 bool gate_bwd_fused_supported(int mode, int N, int C, int ds, int g) {
-  return gatefuse_mode(-1) && gate_bwd_fused_shape(mode, N, C, ds, g);
+  return tune(T_GATEFUSE) && gate_bwd_fused_shape(mode, N, C, ds, g);
 }
 
 long gate_bwd_part_floats(int B, int C) { return (long)(1024 + B) * (2 * C + C / 2 + 1); }

@@ -289,7 +289,8 @@ void gemm_kernel(const GemmK p) {
     //  * with `nfast`, all n-tiles of an m-panel next to each other: a [23040 x 512] activation against a 512 x 512
     //    weight fetched its activation once per n-tile (96 MB for 24) when m ran fastest.
     const int ntile = p.tiles_m * p.tiles_n;
-    if (p.nfast < 0) {               // DGSCT_GEMM_NFAST=-2: the round-1 order (per (y, z) plane, m fastest), kept for A/B runs
+    if (p.nfast < 0) {               // the round-1 order (per (y, z) plane, m fastest).  No host path passes a negative value any more; the arm
+                                     // stays so that the kernel's code is the parent's, instruction for instruction (profiles/switch_cleanup_bench.txt)
       int t = blockIdx.x;
       const int q = ntile >> 3, r = ntile & 7, x = t & 7, y = t >> 3;
       t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
@@ -725,15 +726,9 @@ void gemm_prof_collect(long* launches, double* total_ms, double* total_flops) {
 // ---- per-call time line (diagnostics): one event pair per adapter forward / backward call on ITS stream, so the overlap of the
 // two adapter streams can be read without a tracer in the way (rocprofv3 --kernel-trace makes the late stages host-bound).
 struct CallRec { hipEvent_t e0, e1; int kind, N, C; void* stream; };
-static std::atomic<int> g_call_on{0};
 static std::deque<CallRec>* g_calls = nullptr;
-int call_prof_mode(int set) {
-  const int old = g_call_on.load();
-  if (set == 0 || set == 1) g_call_on.store(set);
-  return old;
-}
 void* call_prof_begin(void* stream, int kind, int N, int C) {
-  if (!g_call_on.load(std::memory_order_relaxed)) return nullptr;
+  if (!tune(T_CALLPROF)) return nullptr;
   CallRec r{nullptr, nullptr, kind, N, C, stream};
   (void)hipEventCreate(&r.e0);
   (void)hipEventCreate(&r.e1);
@@ -782,10 +777,6 @@ static void launch_cfg(const GemmK& k, int ak, int bk, dim3 grid, hipStream_t s,
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// what-if switch (TIMING ONLY, results wrong): split-K partial tiles leave as plain stores instead of fp32 atomics -- what the atomics cost
-static std::atomic<int> g_noatomic{0};
-int gemm_noatomic_mode(int set) { const int old = g_noatomic.load(); if (set >= 0) g_noatomic.store(set); return old; }
 
 template <int MODE>
 static void gemm_mode(const Ctx& ctx, const Gemm& g) {
@@ -853,8 +844,7 @@ static void gemm_mode(const Ctx& ctx, const Gemm& g) {
     // 32-row tiles three times: 98.6 -> 67.2 us at 96 x 96 x 655 360, 67.5 -> 60.8 at 128 x 128 x 368 640
     // (tools/gemm_wgrad_probe.py).
     cfg = g.N <= 96 ? 1 : 0;
-    static const int fs = getenv("DGSCT_GEMM_FORCESPLIT") ? atoi(getenv("DGSCT_GEMM_FORCESPLIT")) : 256;
-    force_split = fs;
+    force_split = 256;
   } else if (g.atomic && g.M >= 1024 && g.N >= 1024 && kflat >= 8192) cfg = 0;   // dWn: a plain big GEMM
   else if (g.atomic && g.M <= 128 && g.M % 64 != 0 && g.M % 32 == 0) cfg = 3;     // 96-row weight gradients: 3 x 32 rows
   else {
@@ -873,8 +863,7 @@ static void gemm_mode(const Ctx& ctx, const Gemm& g) {
   }
   const int ak = g.A.kmajor, bk = g.B.kmajor;
   // FAST staging: 16-byte chunks are aligned and never straddle a matrix edge or a frame of a two-level contraction
-  static const bool no_fast = getenv("DGSCT_GEMM_NOFAST") != nullptr;
-  const bool fast_ok = MODE == DT_BF16 && !no_fast && k.a_vec && k.b_vec && g.K % VE == 0 && (long)g.K * g.KB >= VE &&
+  const bool fast_ok = MODE == DT_BF16 && k.a_vec && k.b_vec && g.K % VE == 0 && (long)g.K * g.KB >= VE &&
                     (ak || g.M % VE == 0) && (bk || g.N % VE == 0) && g.M >= VE && g.N >= VE;
   const int fast = fast_ok ? 1 : 0;
   if (cfg >= 5 && !(MODE == DT_BF16 && fast_ok)) cfg = 1;        // big tiles exist for FAST bf16 only
@@ -889,13 +878,13 @@ static void gemm_mode(const Ctx& ctx, const Gemm& g) {
     splitk = force_split ? force_split : (int)((1024 + wg - 1) / wg);
     // Every split ends in one fp32 atomic per output element, and atomics on one address serialise at the memory side
     // (~0.1 us each): 480 splits of a 36 x 64 weight gradient spent 50 of 58 us there.  Step time vs cap (B=16): none 67.5,
-    // 64: 67.0, 40: 66.6, 32: 66.7, 24: 67.7, 16: 72.2 ms.  DGSCT_GEMM_MAXSPLIT=0 removes the cap.
-    static const int max_split = getenv("DGSCT_GEMM_MAXSPLIT") ? atoi(getenv("DGSCT_GEMM_MAXSPLIT")) : 40;
+    // 64: 67.0, 40: 66.6, 32: 66.7, 24: 67.7, 16: 72.2 ms.
+    constexpr int max_split = 40;
     {   // ... but a workgroup should not walk more than ~32 k-tiles either (655 360-row contractions: 40 splits = 256 k-tiles
         // each, 414 us for a 48 x 6 weight gradient that took 126 us at 512 splits)
       const int deep = k.kt_total / 32;
       const int cap = max_split > deep ? max_split : deep;
-      if (max_split > 0 && !force_split && splitk > cap) splitk = cap;
+      if (!force_split && splitk > cap) splitk = cap;
     }
     int maxs = k.kt_total / 4; if (maxs < 1) maxs = 1;
     if (splitk > maxs) splitk = maxs;
@@ -906,11 +895,9 @@ static void gemm_mode(const Ctx& ctx, const Gemm& g) {
   dim3 grid(k.tiles_m * k.tiles_n, g.batch, splitk);
   k.xgm = k.xnb = 0;
   // n fastest when there are fewer n- than m-tiles: the window of tiles resident on an XCD then spans whole rows of tiles
-  // (each big-operand panel is fetched once; the small operand once per XCD).  DGSCT_GEMM_NFAST=0|1 forces it.
-  static const int nfast_env = getenv("DGSCT_GEMM_NFAST") ? atoi(getenv("DGSCT_GEMM_NFAST")) : -1;
-  k.nfast = nfast_env >= 0 ? nfast_env : nfast_env == -2 ? -1 : (k.tiles_n < k.tiles_m);
-  static const bool no_xgroup = getenv("DGSCT_GEMM_NOXGROUP") != nullptr;
-  if (!no_xgroup && g.A.bs == 0 && g.B.bs != 0 && g.batch >= 16 && g.batch % 8 == 0 && k.tiles_n == 1 && k.tiles_m >= 2 && splitk == 1 &&
+  // (each big-operand panel is fetched once; the small operand once per XCD).
+  k.nfast = k.tiles_n < k.tiles_m;
+  if (g.A.bs == 0 && g.B.bs != 0 && g.batch >= 16 && g.batch % 8 == 0 && k.tiles_n == 1 && k.tiles_m >= 2 && splitk == 1 &&
       kflat >= 512) {
     const int resident = (cfg == 5 ? 1 : (cfg == 0 && ak != bk) ? 2 : 3) * 32;          // workgroups per XCD (launch bounds)
     int gm = (int)(sqrt((double)resident * g.N / BMs[cfg]) + 0.5);
@@ -920,7 +907,7 @@ static void gemm_mode(const Ctx& ctx, const Gemm& g) {
     k.xgm = (k.tiles_m + ngroups - 1) / ngroups;
     k.xnb = g.batch / 8;
   }
-  if (g_noatomic.load(std::memory_order_relaxed)) k.atomic = 0;
+  if (tune(T_NOATOMIC)) k.atomic = 0;      // what-if switch (TIMING ONLY, results wrong): split-K partial tiles leave as plain stores -- what the atomics cost
   hipStream_t s = (hipStream_t)ctx.stream;
   ProfRec shp{};
   shp.M = g.M; shp.N = g.N; shp.K = g.K; shp.KB = g.KB; shp.batch = g.batch; shp.splitk = splitk; shp.cfg = cfg;

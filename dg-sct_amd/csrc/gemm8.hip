@@ -23,7 +23,6 @@
 //     for split-K.
 // One workgroup per CU (112 / 128 KB of LDS): grids are sized in whole rounds of 256 workgroups where the shape allows.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 #include "prims.h"
@@ -76,7 +75,6 @@ struct G8 {
   const char* R;                          // bf16 residual laid out like D (ldd, dbs), added in the row pass (plain stores only); NULL: none
   int gm;                                 // m-tiles per group of the work list (tile order, see the kernel)
   int stag;                               // staggered DMA issue of the two wave halves (dgsct_test_tune "g8stag")
-  int dbg;                                // DGSCT_GEMM8_DBG (timing experiment, results unchanged): 16 = s_setprio 1 around every MFMA group
 };
 
 template <bool KM, int ROWS>
@@ -280,15 +278,12 @@ void gemm8_kernel(const G8 p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) g8_tie(fb[S][j]);
   };
-  const bool prio = p.dbg & 16;                              // experiment: s_setprio 1 around every MFMA group
   auto mmap = [&](int S) {
-    if (prio) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g8_val(fa[S][i]), g8_val(fb[S][j]), acc[i][j], 0, 0, 0);
-    if (prio) __builtin_amdgcn_s_setprio(0);
   };
   // (round 6, p.stag) The two waves of a SIMD are waves w and w + NW / 2.  In lock-step both issue their 7 LDS-DMA instructions of the
   // tile after next right behind the barrier (~100 cycles each beside reads and MFMAs) while the SIMD's matrix pipe has nothing to do.
@@ -426,18 +421,8 @@ static void g8_launch(const G8& k, int ak, int bk, bool batched, bool two, dim3 
   else if (!ak && bk) g8_launch_lay<false, true, BN>(k, batched, two, grid, s);
   else                g8_launch_lay<false, false, BN>(k, batched, two, grid, s);
 }
-static std::atomic<int> g_g8stag{getenv("DGSCT_G8STAG") ? atoi(getenv("DGSCT_G8STAG")) : 1};      // 1: the upper wave half issues behind the first MFMA group of the next iteration (default), 0: lock-step
-int gemm8_stag_mode(int set) { const int old = g_g8stag.load(); if (set >= 0) g_g8stag.store(set ? 1 : 0); return old; }
-
 static inline bool g8_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline double g8_eff(long wgs) { return (double)wgs / (double)(((wgs + 255) / 256) * 256); }
-
-int gemm8_mode(int set) {
-  static std::atomic<int> mode{getenv("DGSCT_GEMM8") ? atoi(getenv("DGSCT_GEMM8")) : 1};
-  const int old = mode.load(std::memory_order_relaxed);
-  if (set >= 0) mode.store(set, std::memory_order_relaxed);
-  return old;
-}
 
 // Late-stage weight gradients (few 256 x 256 output tiles, a 23 040 .. 40 960-row contraction) run on this kernel with only as many
 // split-K slabs as give ~G8_WG_TARGET workgroups: a FEW CUs for longer instead of every CU for a short burst that ends in 16-40-way
@@ -448,7 +433,7 @@ constexpr int G8_WG_TARGET = 32;
 
 bool gemm8_try(const Ctx& ctx, const Gemm& g) {
   // DGSCT_GEMM8=0 switches the kernel off (A/B runs against the tiled engine); =2 also takes shapes below the size gates
-  const int mode = gemm8_mode(-1);
+  const int mode = tune(T_GEMM8);
   if (!mode || ctx.mode != DT_BF16) return false;
   if (g.R && (g.atomic || g.R2 || g.ddt != DT_BF16 || g.rdt != DT_BF16 || g.ldr != g.ldd || g.rbs != g.dbs || g.beta != 1.f || !g8_al16(g.R))) return false;
   if (g.act != ACT_NONE || g.mask || g.R2 || g.bias_m || g.alpha_ptr || g.alpha != 1.f || g.sm_scale || g.sm_dot) return false;
@@ -549,9 +534,7 @@ split_done:
   k.R = (const char*)g.R;
   static const int gm_env = getenv("DGSCT_GEMM8_GM") ? atoi(getenv("DGSCT_GEMM8_GM")) : 4;
   k.gm = gm_env < 1 ? 1 : (gm_env > tiles_m ? tiles_m : gm_env);
-  static const int dbg_env = getenv("DGSCT_GEMM8_DBG") ? atoi(getenv("DGSCT_GEMM8_DBG")) : 0;
-  k.dbg = dbg_env & 16;
-  k.stag = g_g8stag.load(std::memory_order_relaxed);
+  k.stag = tune(T_G8STAG);                                      // 1: the upper wave half issues behind the first MFMA group of the next iteration (default), 0: lock-step
   dim3 grid((unsigned)tiles, splitk, 1);
   hipStream_t s = (hipStream_t)ctx.stream;
   GemmProfShape shp{g.M, g.N, g.K, g.KB, g.batch, splitk, BN == 256 ? 8 : 9, g.A.kmajor, g.B.kmajor, g.atomic, !g.atomic, 0.0};

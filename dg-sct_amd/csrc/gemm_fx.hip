@@ -15,8 +15,6 @@
 // Kernel skeleton = gemm.hip's FAST path (unconditional clamped 16-byte loads, two register sets in flight, [rows][64 + 8] LDS
 // tiles, v_mfma_f32_32x32x16_bf16, XCD-chunked work list, rows through LDS as 16-byte stores).
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "err.h"
@@ -399,8 +397,6 @@ void gemm_fx_kernel(const FxK p) {
   }
 }
 
-std::atomic<int> g_fx_mode{-1};
-
 template <int WGM, int WGN, int TM, int TN, int PRO, int EPI>
 void fx_launch_one(const FxK& k, dim3 grid, size_t shmem, hipStream_t s) {
   auto kern = gemm_fx_kernel<WGM, WGN, TM, TN, PRO, EPI>;
@@ -450,19 +446,8 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-int gemmfx_mode(int set) {
-  // bit mask of the call sites (plan.cpp): 1 dZ (BN2 backward), 2 dX3 (ReLU + BN1 backward), 4 dXc (ReLU backward + channel-gate backward),
-  // 8 dX1 += dvq1 Wv1 (ReLU backward); 15 = all (default); 16: the A-operand prologues of sites 4 / 8 at every width (default: C <= 256);
-  // 32: site 4 never with its prologue (tests); FORWARD sites: 64 vq1 product + per-frame column sums / positive counts, 128 the two
-  // bottleneck products + their BatchNorm sums; default = 15 + 64 + 128
-  if (g_fx_mode.load(std::memory_order_relaxed) < 0) g_fx_mode.store(getenv("DGSCT_NO_GEMMFX") ? 0 : 15 + 64 + 128, std::memory_order_relaxed);
-  const int old = g_fx_mode.load(std::memory_order_relaxed);
-  if (set >= 0) g_fx_mode.store(set & 255, std::memory_order_relaxed);
-  return old;
-}
-
 bool gemm_fx_supported(const Ctx& ctx, const Gemm& g, const GemmFx& fx) {
-  if (!gemmfx_mode(-1) || ctx.mode != DT_BF16) return false;
+  if (!tune(T_GEMMFX) || ctx.mode != DT_BF16) return false;
   if (!g.A.kmajor || !g.B.kmajor || g.KB != 1 || g.atomic || g.splitk > 1 || g.ddt != DT_BF16) return false;
   if ((g.act != ACT_NONE && g.act != ACT_RELU) || g.mask || g.R2 || g.bias_m || g.r1_m || g.r1_n || g.alpha_ptr || g.alpha != 1.f || g.sm_scale || g.sm_dot) return false;
   if (g.bias_n_bs != 0 || (g.R && (g.rdt != DT_BF16 || g.beta != 1.f))) return false;

@@ -13,22 +13,16 @@ void gemm_prof_end(void* rec, void* stream);
 // Launches `g` on the 8-wave kernel when it qualifies (bf16, deep contraction, 256-row tiles, plain epilogue) and
 // returns true; false = not eligible, the caller runs the tiled engine.
 bool gemm8_try(const Ctx& ctx, const Gemm& g);
-// 0: off, 1: on for shapes that fill the chip (default; DGSCT_GEMM8), 2: on for every eligible shape (tests).  set < 0: query.
-int gemm8_mode(int set);
+// tune(T_GEMM8): 0 off, 1 on for shapes that fill the chip (default; DGSCT_GEMM8 sets the initial value), 2 on for every eligible shape (tests).
 
 // Skinny products (M <= 256 rows, both operands K-major: the per-frame gate MLPs): one 32 x 32 tile per workgroup, contraction split
 // over its four waves, operands straight to registers (gemm_skinny.hip).  Same contract as gemm8_try.
 bool gemm_skinny_try(const Ctx& ctx, const Gemm& g);
-int gemm_skinny_mode(int set);      // 0: off, 1: on (default; DGSCT_GEMM_SKINNY).  set < 0: query.
 
 // Weight gradients over the token rows (both operands [rows][width], a small output, a very deep contraction): one stream over the
 // two tensors, output tiles dealt to the waves (gemm_tall.hip).  Same contract as gemm8_try.  CONTRACT: MN-major operands handed to gemm() must point at
 // COLUMN 0 of their [rows][ld] tensor (a column slab is selected with `bs`, not by offsetting the base pointer): this kernel reads
 // whole ld-wide rows from the pointer, and an offset base would run past the end of the tensor in the last 64-row block.
 bool gemm_tall_try(const Ctx& ctx, const Gemm& g);
-int gemm_tall_mode(int set);        // 0: off, 1: on (default; DGSCT_NO_GEMM_TALL).  set < 0: query.
-
-int gemm8_stag_mode(int set);      // (round 6) the two wave halves issue their LDS-DMA shares a quarter k-tile apart (1) or in lock-step (0)
-int gemm_noatomic_mode(int set);   // what-if (timing only): split-K partials as plain stores
 
 }  // namespace dgsct

@@ -14,8 +14,6 @@
 // can pull are spread over M/32 x N/32 = 40-160 CUs instead of 24.  Epilogue: bias, ReLU / sigmoid, ReLU mask of
 // another tensor, residual; fp32 or bf16 out as 16- / 8-byte row pieces.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "err.h"
@@ -230,15 +228,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_k(const SkFuse p) {
   else stv<DT_BF16, 4>(p.D, (long)m * p.ldd + n, v);
 }
 
-int skfuse_mode(int set) {
-  static std::atomic<int> mode{getenv("DGSCT_NO_SKFUSE") ? 0 : 1};
-  const int old = mode.load(std::memory_order_relaxed);
-  if (set >= 0) mode.store(set ? 1 : 0, std::memory_order_relaxed);
-  return old;
-}
-
 bool skinny_fused_supported(const Ctx& ctx, int M, int N, int K, int K2) {
-  if (!skfuse_mode(-1) || !gemm_skinny_mode(-1) || ctx.mode != DT_BF16) return false;
+  if (!tune(T_SKFUSE) || !tune(T_SKINNY) || ctx.mode != DT_BF16) return false;
   if (M < 1 || M > 256 || N < 32 || N % 4) return false;
   if (K < 64 || K % 64 || K > 4096) return false;
   if (K2 && (K2 < 64 || K2 % 64 || K2 > 4096)) return false;
@@ -268,15 +259,8 @@ void skinny_fused(const Ctx& ctx, const SkFuse& p) {
 
 static inline bool sk_al(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
-int gemm_skinny_mode(int set) {     // process-wide, test-only switch (like gemm8_mode / rowfuse_mode): atomic, DataParallel replicas run on threads
-  static std::atomic<int> mode{getenv("DGSCT_GEMM_SKINNY") ? atoi(getenv("DGSCT_GEMM_SKINNY")) : 1};
-  const int old = mode.load(std::memory_order_relaxed);
-  if (set >= 0) mode.store(set, std::memory_order_relaxed);
-  return old;
-}
-
 bool gemm_skinny_try(const Ctx& ctx, const Gemm& g) {
-  if (!gemm_skinny_mode(-1) || ctx.mode != DT_BF16) return false;
+  if (!tune(T_SKINNY) || ctx.mode != DT_BF16) return false;
   if (g.batch != 1 || g.KB != 1 || g.atomic || g.splitk > 1) return false;
   if (!g.A.kmajor || !g.B.kmajor) return false;
   if (g.M < 1 || g.M > 256 || g.N < 32 || g.N % 4) return false;

@@ -12,8 +12,6 @@
 // contraction.  The (group, m-tile, n-tile) tiles of the output are dealt round-robin to the four waves (<= 4 tiles = 64
 // accumulator registers each); at the end every wave adds its tiles to D with fp32 atomics.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "mma_tile.h"
@@ -111,19 +109,10 @@ __global__ __launch_bounds__(256) void gemm_tall_k(const GT p) {
     }
   }
 }
-
-std::atomic<int> g_tall{-1};
 }  // namespace
 
-int gemm_tall_mode(int set) {
-  if (g_tall.load(std::memory_order_relaxed) < 0) g_tall.store(getenv("DGSCT_NO_GEMM_TALL") ? 0 : 1, std::memory_order_relaxed);
-  const int old = g_tall.load(std::memory_order_relaxed);
-  if (set >= 0) g_tall.store(set > 2 ? 1 : set, std::memory_order_relaxed);
-  return old;
-}
-
 bool gemm_tall_try(const Ctx& ctx, const Gemm& g0) {
-  if (!gemm_tall_mode(-1) || ctx.mode != DT_BF16) return false;
+  if (!tune(T_GEMMTALL) || ctx.mode != DT_BF16) return false;
   Gemm g = g0;
   // a two-level contraction over (frame, row) whose frames lie back to back in BOTH operands is one flat stream of KB * K rows
   // (dWc of the audio direction: sum_b dT2[b]^T Y[b])
@@ -134,7 +123,7 @@ bool gemm_tall_try(const Ctx& ctx, const Gemm& g0) {
   // tall only; whole 64-row blocks.  Default gate = the stage-0 depths (368 640 / 655 360 rows): in the step the stage-1 products
   // (92 160 / 163 840 rows) measured +30..+47 us per pair with this kernel although each is as fast or faster alone
   // (tools/call_overlap.py AB=gemmtall); "gemmtall" = 2 takes everything from 16 384 rows (tests)
-  const long kmin = gemm_tall_mode(-1) >= 2 ? 16384 : 262144;
+  const long kmin = tune(T_GEMMTALL) >= 2 ? 16384 : 262144;
   if (g.K < kmin || g.K % GT_RB) return false;
   if (g.A.ld > GT_MAXW || g.B.ld > GT_MAXW) return false;
   if (g.A.ld % 4 || g.B.ld % 4) return false;                // 8-byte aligned transpose reads

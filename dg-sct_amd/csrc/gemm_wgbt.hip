@@ -10,8 +10,6 @@
 // at a time as 16-byte chunks into LDS and read back transposed (ds_read_b64_tr_b16) as the operands of v_mfma_f32_32x32x16_bf16; wave w
 // computes the 32 x 32 quadrant (w >> 1, w & 1).  Plain fp32 stores (each output has one writer).
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 #include "prims.h"
 #include "device_util.h"
 #include "mma_tile.h"
@@ -75,19 +73,10 @@ __global__ __launch_bounds__(256) void wgrad_bt_k(const WgBtK t) {
     }
   }
 }
-
-std::atomic<int> g_wgbt{-1};
 }  // namespace
 
-int wgrad_bt_mode(int set) {
-  if (g_wgbt.load(std::memory_order_relaxed) < 0) g_wgbt.store(getenv("DGSCT_NO_WGBT") ? 0 : 1, std::memory_order_relaxed);
-  const int old = g_wgbt.load(std::memory_order_relaxed);
-  if (set >= 0) g_wgbt.store(set ? 1 : 0, std::memory_order_relaxed);
-  return old;
-}
-
 bool wgrad_bt_supported(const Ctx& ctx, const WgBtJob* jobs, int n) {
-  if (!wgrad_bt_mode(-1) || ctx.mode != DT_BF16 || n < 1 || n > WGBT_MAX) return false;
+  if (!tune(T_WGBT) || ctx.mode != DT_BF16 || n < 1 || n > WGBT_MAX) return false;
   for (int i = 0; i < n; ++i) {
     const WgBtJob& j = jobs[i];
     if (!j.A || !j.B || !j.D || j.M < 1 || j.N < 1 || j.K < 1) return false;

@@ -11,7 +11,6 @@
 #include "plan.h"
 #include <cstdlib>
 
-#include <atomic>
 #include <functional>
 #include <vector>
 
@@ -81,10 +80,6 @@ bool Plan::validate() {
 //   1024 the [rows, C] x [C, C] chain GEMMs (vq1, vq2, dXc, dX1 +=)    2048 the remap GEMMs    4096 the bottleneck GEMMs
 //   8192 the backward's final join with the aux stream    16384 / 32768 / 65536 / 131072: tokattn_fwd / xattn_fwd / xattn_bwd / tokattn_bwd alone
 // "skipminc": only for adapters at least that wide (default 0).
-static std::atomic<int> g_skip{0}, g_skip_minc{0}, g_skip_maxc{1 << 30};
-int plan_skip_mode(int set) { const int old = g_skip.load(); if (set >= 0) g_skip.store(set); return old; }
-int plan_skip_minc(int set) { const int old = g_skip_minc.load(); if (set >= 0) g_skip_minc.store(set); return old; }
-int plan_skip_maxc(int set) { const int old = g_skip_maxc.load(); if (set >= 0) g_skip_maxc.store(set ? set : (1 << 30)); return old; }
 
 void Plan::layout() {
   // ---- prep: E copies of the GEMM weights (bf16 mode only) + derived fp32 vectors
@@ -370,7 +365,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
   Ctx side = ctx;
   if (aux_stream) { side.stream = aux_stream; side.aux = nullptr; }
   const float invN = 1.f / (float)N;
-  const int SK = (C >= g_skip_minc.load(std::memory_order_relaxed) && C <= g_skip_maxc.load(std::memory_order_relaxed)) ? g_skip.load(std::memory_order_relaxed) : 0;   // what-if switches
+  const int SK = (C >= tune(T_SKIPMINC) && C <= tune(T_SKIPMAXC)) ? tune(T_SKIP) : 0;   // what-if switches
   zero(ctx, b.S(0), (size_t)s.zero_end);
 
   // F1 ---- cross-modal remap                                            net_trans.py:553-555
@@ -437,7 +432,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
       // stages 0 (C = 96 / 128): only mean_N vq1 exists -- one pass over X1, the [rows, C] tensor is never written (the backward
       // recomputes the ReLU decisions from X1: vq1_bwd)
       vq1sum_fwd(ctx, b.S(s.X1), b.W(DGSCT_P_WV1), b.F(DGSCT_P_BV1), B, N, C, invN, b.S<float>(s.mvq1),
-                 vq1fuse_mode(-1) == 2 ? b.S(s.vq1) : nullptr);
+                 tune(T_VQ1FUSE) == 2 ? b.S(s.vq1) : nullptr);
     } else {
       bool vq1_summed = false;
       Gemm g3 = mk((int)R, C, C);                                // vq1 = relu(X1 Wv1^T + b)
@@ -447,7 +442,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
       else {
         // (round 5) the per-frame column sums (mean_N vq1) and positive counts in the product's epilogue: no second pass over vq1
         GemmFx fv; fv.epi = EPI_COLSUM; fv.rpf = N; fv.e_acc = b.S<float>(s.mvq1); fv.e_acc2 = b.S<float>(s.cnt1); fv.e_ld = C; fv.e_scale = invN;
-        if ((gemmfx_mode(-1) & 64) && gemm_fx_supported(ctx, g3, fv)) { if (!(SK & 1024)) gemm_fx(ctx, g3, fv); vq1_summed = true; }
+        if ((tune(T_GEMMFX) & 64) && gemm_fx_supported(ctx, g3, fv)) { if (!(SK & 1024)) gemm_fx(ctx, g3, fv); vq1_summed = true; }
         else if (!(SK & 1024)) gemm(ctx, g3);
       }
       // mean_N vq1, and the number of positive entries per (frame, channel) for the backward (same pass over vq1)
@@ -489,7 +484,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
                 d.temporal ? b.S<float>(s.tg) : nullptr, d.alpha, d.beta, d.gamma, d.ln_before ? b.F(DGSCT_P_LNB_W) : nullptr,
                 d.ln_before ? b.F(DGSCT_P_LNB_B) : nullptr, d.eps, B, N, C, ds, g, b.F(DGSCT_P_WD), b.S<float>(s.sl), b.S(s.X3),
                 b.S<float>(s.mu_b), b.S<float>(s.rstd_b), b.S(s.Zp), d.use_bn && d.training ? b.S<float>(s.bnacc1) : nullptr,
-                (!bfuse || gatefuse_mode(-1) == 2) ? b.S(s.vq2) : nullptr);
+                (!bfuse || tune(T_GATEFUSE) == 2) ? b.S(s.vq2) : nullptr);
     spatial_fwd(ctx, b.S<float>(s.sl), B, N, b.S<float>(s.sg), b.S<float>(s.map), map);   // saved copy + the returned map
   } else {
     void* Xcf = xc_scratch ? b.Wk(wf.Xc) : b.S(s.Xc);
@@ -531,7 +526,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
       g1.B = km(b.W(DGSCT_P_WD), C / g, (long)(ds / g) * (C / g));
       outE(g1, b.S(s.Zp), E, ds, ds / g);
       GemmFx f1s; f1s.epi = EPI_COLSTATS; f1s.e_acc = b.S<float>(s.bnacc1) + ds; f1s.e_acc2 = b.S<float>(s.bnacc1) + 2 * ds;
-      if (d.use_bn && d.training && (gemmfx_mode(-1) & 128) && gemm_fx_supported(ctx, g1, f1s)) {       // BN1 sums in the epilogue
+      if (d.use_bn && d.training && (tune(T_GEMMFX) & 128) && gemm_fx_supported(ctx, g1, f1s)) {       // BN1 sums in the epilogue
         if (!(SK & 4096)) gemm_fx(ctx, g1, f1s);
         stats1_done = true;
       } else if (!(SK & 4096)) gemm(ctx, g1);
@@ -553,7 +548,7 @@ int Plan::forward(float* const* params, const void* prep, const void* X, const v
       g2.B = km(b.W(DGSCT_P_WU), ds / g, (long)(C / g) * (ds / g));
       outE(g2, b.S(s.Op), E, C, C / g);
       GemmFx f2s; f2s.epi = EPI_COLSTATS; f2s.e_acc = b.S<float>(s.bnacc2) + C; f2s.e_acc2 = b.S<float>(s.bnacc2) + 2 * C;
-      if (stats2 && (gemmfx_mode(-1) & 128) && gemm_fx_supported(ctx, g2, f2s)) {                       // BN2 sums in the epilogue
+      if (stats2 && (tune(T_GEMMFX) & 128) && gemm_fx_supported(ctx, g2, f2s)) {                       // BN2 sums in the epilogue
         if (!(SK & 4096)) gemm_fx(ctx, g2, f2s);
         stats2_done = true;
       } else if (!(SK & 4096)) gemm(ctx, g2);
@@ -605,7 +600,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     gemm(ctx, g3);
   };
   if (phase == 2) {
-    const int sk2 = (C >= g_skip_minc.load(std::memory_order_relaxed) && C <= g_skip_maxc.load(std::memory_order_relaxed)) ? g_skip.load(std::memory_order_relaxed) : 0;
+    const int sk2 = (C >= tune(T_SKIPMINC) && C <= tune(T_SKIPMAXC)) ? tune(T_SKIP) : 0;
     if (!(sk2 & 2048)) dy_product();                          // (what-if switch: the remap products)
     check_async("dgsct_adapter_backward (dY product)");
     return has_error() ? 1 : 0;
@@ -634,7 +629,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
   const int cg = C / g, dg = ds / g;
   const float invN = 1.f / (float)N;
   const bool vproj = gproj_supported(ctx.mode, C, ds, g);
-  const int SK = (C >= g_skip_minc.load(std::memory_order_relaxed) && C <= g_skip_maxc.load(std::memory_order_relaxed)) ? g_skip.load(std::memory_order_relaxed) : 0;   // what-if switches
+  const int SK = (C >= tune(T_SKIPMINC) && C <= tune(T_SKIPMAXC)) ? tune(T_SKIP) : 0;   // what-if switches
   // (weight-gradient products on the aux stream: every one of them goes through wgemm)
   auto wgemm = [SK](const Ctx& c, const Gemm& gg) { if (!(SK & 1)) gemm(c, gg); };
 
@@ -658,7 +653,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     outE(gdz, b.Wk(wb.dZ), E, ds, dg);
     fdz.a_pro = APRO_BNBWD; fdz.a2 = b.S(s.Op); fdz.bn_mean = bn2; fdz.bn_rstd = bn2 + C; fdz.bn_sc = bn2 + 2 * C; fdz.bn_sh = bn2 + 3 * C;
     fdz.bn_sums = G(DGSCT_P_BN2_B); fdz.bn_rows = R; fdz.bn_C = C; fdz.bn_relu = 0; fdz.bn_training = d.training; fdz.a_store = dO;
-    fx_dz = (gemmfx_mode(-1) & 1) && gemm_fx_supported(ctx, gdz, fdz);
+    fx_dz = (tune(T_GEMMFX) & 1) && gemm_fx_supported(ctx, gdz, fdz);
   }
   if (d.use_bn && !bnb && !fx_dz && !(SK & 8)) {
     bn_bwd_apply(ctx, dO, b.S(s.Op), dO, R, C, bn2, bn2 + C, bn2 + 2 * C, bn2 + 3 * C, G(DGSCT_P_BN2_B), 0, 1, d.training);
@@ -729,7 +724,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     outE(gdx3, b.Wk(wb.dX3), E, C, cg);
     fdx3.a_pro = APRO_BNBWD; fdx3.a2 = b.S(s.Zp); fdx3.bn_mean = bn1; fdx3.bn_rstd = bn1 + ds; fdx3.bn_sc = bn1 + 2 * ds; fdx3.bn_sh = bn1 + 3 * ds;
     fdx3.bn_sums = G(DGSCT_P_BN1_B); fdx3.bn_rows = R; fdx3.bn_C = ds; fdx3.bn_relu = 1; fdx3.bn_training = d.training; fdx3.a_store = b.Wk(wb.dZp);
-    fx_dx3 = (gemmfx_mode(-1) & 2) && gemm_fx_supported(ctx, gdx3, fdx3);
+    fx_dx3 = (tune(T_GEMMFX) & 2) && gemm_fx_supported(ctx, gdx3, fdx3);
   }
   if (fx_dx3) {
   } else if (SK & 8) {
@@ -777,7 +772,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     GemmFx fxc;
     fxc.epi = EPI_XCBWD; fxc.rpf = N;
     fxc.e_cs = b.S<float>(s.ch); fxc.e_x = b.S(s.X1); fxc.e_acc = b.Wk<float>(wb.dch); fxc.e_ld = C;
-    const int fxm = gemmfx_mode(-1);
+    const int fxm = tune(T_GEMMFX);
     int fx_xc = 0;                                               // 0: separate launches, 1: epilogue only, 2: prologue + epilogue
     if (fxm & 4) {
       gxc.A = km(b.S(s.vq2), dd);
@@ -906,7 +901,7 @@ int Plan::backward(float* const* params, const void* prep, const void* X, const 
     GemmFx fx1;
     fx1.a_pro = APRO_MASKSCALE; fx1.rpf = N; fx1.a_cs = b.Wk(wb.coef); fx1.a_cs_dt = DT_F32; fx1.a_cs_ld = C; fx1.a_scale = 1.f / (float)N;
     fx1.a_store = b.Wk(wb.dvq1);
-    fx_x1 = (gemmfx_mode(-1) & 8) && (C <= 256 || (gemmfx_mode(-1) & 16)) && gemm_fx_supported(ctx, gx1, fx1);   // (as for dXc above)
+    fx_x1 = (tune(T_GEMMFX) & 8) && (C <= 256 || (tune(T_GEMMFX) & 16)) && gemm_fx_supported(ctx, gx1, fx1);   // (as for dXc above)
     if (fx_x1) {
       if (!(SK & 1024)) gemm_fx(ctx, gx1, fx1);
       defer([=, &side, &b] {                                     // t1 = E(coef / N) * cnt1: summed over the frames with the other bias gradients

@@ -12,6 +12,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include "tune.h"      // tune(T_...): the dgsct_test_tune switches the primitives and the schedule read
 
 namespace dgsct {
 
@@ -31,7 +32,6 @@ struct PartTable { PartDesc d[4]; int NQ, C; };
 struct PartJob { const float* part = nullptr; PartTable t; int n = 0; };
 void part_reduce_run(void* stream, const PartJob&);
 // diagnostics: event pair around every adapter call on its stream (dgsct_test_tune "callprof": 1 on, 0 off, 2 dump to $DGSCT_CALL_PROF)
-int call_prof_mode(int set);
 void* call_prof_begin(void* stream, int kind, int N, int C);
 void call_prof_end(void* rec);
 void call_prof_dump(const char* path);
@@ -119,7 +119,6 @@ struct GemmFx {
 // plain D = A' B^T (+ bias_n, + R) in E; g carries the operands / output as for gemm()
 bool gemm_fx_supported(const Ctx&, const Gemm&, const GemmFx&);
 void gemm_fx(const Ctx&, const Gemm&, const GemmFx&);
-int gemmfx_mode(int set);          // dgsct_test_tune "gemmfx": bit mask of the fused call sites (1 dZ, 2 dX3, 4 dXc, 8 dX1; 15 default, 0 = the separate launches); set < 0: query
 // A [BT, C] gate-MLP product with its neighbouring elementwise launches folded in (gemm_skinny.hip; bf16, M <= 256, both operands
 // K-major):   D = epi( act( sum_k A'[m][k] B[n][k] + sum_k2 A2[m][k2] B2[n][k2] + bias_n ) masked by (mask > 0) )
 //   a_mode 0: A' = A (bf16)          1: A' = bf16(A (bf16) * a_mul (fp32))          2: A' = bf16(A (fp32) * s (1 - s)), s = a_mul (fp32)
@@ -133,7 +132,6 @@ struct SkFuse {
   int epi = 0; void* D = nullptr; int ddt = DT_F32; long ldd = 0;
   const float* e_mul = nullptr; long ld_emul = 0; const void* e_q = nullptr; long ld_eq = 0; float* D2 = nullptr; long ldd2 = 0;
 };
-int skfuse_mode(int set);         // dgsct_test_tune "skfuse"
 bool skinny_fused_supported(const Ctx&, int M, int N, int K, int K2);
 void skinny_fused(const Ctx&, const SkFuse&);
 // bench-only: time every GEMM launch of this thread with HIP events (see gemm.hip)
@@ -214,7 +212,6 @@ void gproj_narrow_bnb(const Ctx&, const void* dy, const void* xv, void* dx, long
                       long sj, long sc, void* y, const float* mean, const float* rstd, const float* bsc, const float* bsh, const float* sums, int training);
 // modln_fwd + gproj_narrow + bn_stats(y) in one pass over X1 (lnw may be null; stats null = no sums)
 bool modln_gproj_supported(int mode, int C, int ds, int g);
-int rowfuse_mode(int set);        // test / tuning switch of the fused row passes (dgsct_test_tune "rowfuse")
 void modln_gproj(const Ctx&, const void* X1, const float* ch, const float* sg, const float* tg, float alpha, float beta, float gamma,
                  const float* lnw, const float* lnb, float eps, int B, int N, int C, int ds, int g, const float* W, long wsg, long wsj,
                  long wsc, void* X3, float* mu, float* rstd, void* y, float* stats);
@@ -229,8 +226,7 @@ void gproj_wide(const Ctx&, const void* x, long rows, int C, int ds, int g, cons
 // still want it materialised.
 bool gate_fused_supported(int mode, int N, int C, int ds, int g);
 // 0: off, 1: on (default), 2: on, and the forward still materialises vq2 for inspection (tests pin the device's ReLU decisions).
-// dgsct_test_tune "gatefuse"; set < 0: query
-int gatefuse_mode(int set);
+// dgsct_test_tune "gatefuse"
 void gatemod_fwd(const Ctx&, const void* X1, const float* ch, const void* aq2, const float* Wv2, const float* bv2, const float* ws,
                  const float* bs, const float* tg, float alpha, float beta, float gamma, const float* lnw, const float* lnb, float eps,
                  int B, int N, int C, int ds, int g, const float* Wd, float* sl, void* X3, float* mu, float* rstd, void* Zp,
@@ -247,7 +243,6 @@ bool gate_bwd_fused_supported(int mode, int N, int C, int ds, int g);
 //   vq1sum_fwd: msum[b][c] += invN * sum_n vq1[b][n][c]          (Wv1: the prepared E copy, K-major [C][C])
 //   vq1_bwd:    dvq1 = (vq1 > 0) * E(coef[b][c] * invN) (required; written, E), dbv1[c] += sum dvq1, dX1 += dvq1 Wv1 (in place, E)
 //               part: >= 1024 * C floats of scratch; with ctx.late set the second stage of dbv1 is left to the caller
-int vq1fuse_mode(int set);
 bool vq1_fused_shape(int mode, int N, int C);        // (without the switch: layout decisions)
 bool vq1_fused_supported(int mode, int N, int C);
 void vq1sum_fwd(const Ctx&, const void* X1, const void* Wv1, const float* bv1, int B, int N, int C, float invN, float* msum,
@@ -280,7 +275,6 @@ struct BnFin {
   const float* acc; long rows; const float* w; const float* b; float* run_mean; float* run_var; float momentum, eps; int training;
   float* mean; float* rstd; float* sc; float* sh;
 };
-int bnfold_mode(int set);
 void affine_act_bn(const Ctx&, const void* x, void* y, long rows, int C, const BnFin& fin, int relu);
 // sums[0][c] += sum dyb, sums[1][c] += sum dyb*xh with dyb = dy * (relu ? (x*sc+sh > 0) : 1), xh = (x-mean)*rstd
 void bn_bwd_stats(const Ctx&, const void* dy, const void* x, long rows, int C, const float* mean, const float* rstd,
@@ -319,7 +313,6 @@ constexpr int WGBT_MAX = 4;
 struct WgBtJob { const void* A; const void* B; float* D; int M, N, K; long lda, ldb, ldd; };
 bool wgrad_bt_supported(const Ctx&, const WgBtJob* jobs, int n);
 void wgrad_bt(const Ctx&, const WgBtJob* jobs, int n);
-int wgrad_bt_mode(int set);
 
 // tokpk (optional, bf16 mode): the latent tokens PACKED for the wave-centric fast kernels (attn2.hip): per frame
 // [hi 32 x C | lo 32 x C | transposed C x 32] bf16 = tok_pack_elems(B, C) elements; consumers fall back to the generic

@@ -9,7 +9,6 @@
 //  * "column-strip" kernels (per-channel affine / reductions over tokens): a thread owns VE consecutive
 //    channels and walks rows; loads are 16 B per lane and coalesced along the channel axis.
 // All of them are HBM-bound; they read and write each big tensor exactly once.
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "prims.h"
 #include "device_util.h"
@@ -143,10 +142,7 @@ void zero2(const Ctx& ctx, void* a, size_t abytes, void* b, size_t bbytes) {
 // row-kernel geometry
 // ================================================================================================
 struct RowGeom { int gs, nv, rpp, rpc, chunks; };
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
+constexpr int ROW_MIN_ITERS = 8;      // rows a reduction workgroup streams at least (modln_bwd, tail_bwd), see min_iters below
 // min_iters: a workgroup keeps per-channel constants in registers and (reduction kernels) flushes per-channel sums with
 // one LDS pass + one atomic per channel; it must stream enough rows to amortise that (late stages: 36-144 rows per frame).
 // floor_to_cap: target_wgs is the resident capacity (wg_capacity) -> never exceed one round
@@ -437,17 +433,14 @@ __global__ __launch_bounds__(256) void modln_bwd_k(const void* dX3, const void* 
 void modln_bwd(const Ctx& ctx, const void* dX3, const void* X1, const float* ch, const float* sg, const float* tg,
                float alpha, float beta, float gamma, const float* lnw, const float* mu, const float* rstd, int B, int N,
                int C, void* dX1, float* dlnw, float* dlnb, float* dch, float* dsg, float* dtg, float* part, long part_floats) {
-  static const int mi = env_int("DGSCT_ROW_MIN_ITERS", 8);
-  static const int use_cap = env_int("DGSCT_ROW_CAP", 1);
-  RowGeom g = row_geom(C, row_ve(ctx, C), N, B, 1024, mi);
+  RowGeom g = row_geom(C, row_ve(ctx, C), N, B, 1024, ROW_MIN_ITERS);
   const size_t sh = (size_t)(256 / g.gs) * C * sizeof(float);      // flush_cols: one row of C floats per row-group
-  if (use_cap) {
+  {
     int cap = 1024;
     ROW_CAPACITY(cap, ctx, C, g.nv, modln_bwd_k, sh);
-    g = row_geom(C, row_ve(ctx, C), N, B, cap, mi, true);
+    g = row_geom(C, row_ve(ctx, C), N, B, cap, ROW_MIN_ITERS, true);
   }
-  static const int use_part = env_int("DGSCT_ROW_PART", 1);
-  if (!use_part || (long)g.chunks * B * 3 * C > part_floats) part = nullptr;
+  if ((long)g.chunks * B * 3 * C > part_floats) part = nullptr;
   ROW_DISPATCH_SH(ctx, C, g.nv, modln_bwd_k, dim3(g.chunks, B), sh, dX3, X1, ch, sg, tg, alpha, beta, gamma, lnw, mu, rstd, N, C,
                   g.gs, g.nv, g.rpc, dX1, dlnw, dlnb, dch, dsg, tg ? dtg : nullptr, part);
   if (part) {
@@ -545,7 +538,7 @@ void tail_fwd(const Ctx& ctx, const void* Op, const float* sc2, const float* sh2
               const void* residual, const BnFin* fin2) {
   BnFin fin{};
   int has_fin = 0;
-  if (fin2 && (!bnfold_mode(-1) || rows < 1)) {
+  if (fin2 && (!tune(T_BNFOLD) || rows < 1)) {
     bn_finalize(ctx, fin2->acc, fin2->rows, C, fin2->w, fin2->b, fin2->run_mean, fin2->run_var, fin2->momentum, fin2->eps,
                 fin2->training, fin2->mean, fin2->rstd, fin2->sc, fin2->sh);
   } else if (fin2) {
@@ -734,17 +727,14 @@ void tail_bwd(const Ctx& ctx, const void* dOut, const void* Op, const float* sc2
               const float* rstd2, const float* lnw, const float* lnb, const float* gate, int gate_first, const float* mu,
               const float* rstd, long rows, int C, void* dO, float* dlnw, float* dlnb, float* dgate, float* bnsums,
               float eps, float* part, long part_floats) {
-  static const int mi = env_int("DGSCT_ROW_MIN_ITERS", 8);
-  static const int use_cap = env_int("DGSCT_ROW_CAP", 1);
-  RowGeom g = row_geom(C, row_ve(ctx, C), (int)rows, 1, 1024, mi);
+  RowGeom g = row_geom(C, row_ve(ctx, C), (int)rows, 1, 1024, ROW_MIN_ITERS);
   const size_t sh = (size_t)(256 / g.gs) * C * sizeof(float);      // flush_cols: one row of C floats per row-group
-  if (use_cap) {
+  {
     int cap = 1024;
     ROW_CAPACITY(cap, ctx, C, g.nv, tail_bwd_k, sh);
-    g = row_geom(C, row_ve(ctx, C), (int)rows, 1, cap, mi, true);
+    g = row_geom(C, row_ve(ctx, C), (int)rows, 1, cap, ROW_MIN_ITERS, true);
   }
-  static const int use_part = env_int("DGSCT_ROW_PART", 1);
-  if (!use_part || (long)g.chunks * 4 * C > part_floats) part = nullptr;
+  if ((long)g.chunks * 4 * C > part_floats) part = nullptr;
   if (sc2 && lnw && gate && !gate_first)
     ROW_DISPATCH_SH(ctx, C, g.nv, tail_bwd_ave_k, dim3(g.chunks), sh, dOut, Op, sc2, sh2, mean2, rstd2, lnw, lnb, gate, gate_first,
                     mu, rstd, rows, C, g.gs, g.nv, g.rpc, dO, dlnw, dlnb, dgate, bnsums, part, eps);
@@ -954,8 +944,7 @@ void rowdot_colsum_frames(const Ctx& ctx, const void* x, long ld, long bs, int B
     ROW_CAPACITY(cap, ctx, C, g.nv, rowdot_colsum_fr_k, sh);
     g = row_geom(C, ve, N, B, cap, 4, true);
   }
-  static const int use_part = env_int("DGSCT_ROW_PART", 1);
-  if (!use_part || !out_col || (long)g.chunks * B * C > part_floats) part = nullptr;
+  if (!out_col || (long)g.chunks * B * C > part_floats) part = nullptr;
   ROW_DISPATCH_SH(ctx, C, g.nv, rowdot_colsum_fr_k, dim3(g.chunks, B), sh, x, ld, bs, N, C, w, roww, g.gs, g.nv, g.rpc,
                   out_row ? row_part : nullptr, out_col, part);
   if (out_row) sum_batch(ctx, row_part, N, B, N, out_row, 1.f, 1);
@@ -980,8 +969,7 @@ void rowdot_colsum(const Ctx& ctx, const void* x, long ld, long bs, int B, int N
     ROW_CAPACITY(cap, ctx, C, g.nv, rowdot_colsum_k, sh);
     g = row_geom(C, ve, N, groups, cap, 1, true);
   }
-  static const int use_part = env_int("DGSCT_ROW_PART", 1);
-  if (!use_part || !out_col || (long)g.chunks * groups * C > part_floats) part = nullptr;
+  if (!out_col || (long)g.chunks * groups * C > part_floats) part = nullptr;
   ROW_DISPATCH_SH(ctx, C, g.nv, rowdot_colsum_k, dim3(g.chunks, groups), sh, x, ld, bs, B, N, C, w, roww, g.gs, g.nv, g.rpc, fpg,
                   out_row, out_col, part);
   if (part) {

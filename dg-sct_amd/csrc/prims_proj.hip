@@ -7,7 +7,6 @@
 //   wide:   y[r][gi*cg + cl] = sum_jl x[r][gi*dg + jl] * W(gi, jl, cl)     [rows][ds] -> [rows][C]  (+ BatchNorm sums)
 // W(gi, jl, cl) = W[gi*sg + jl*sj + cl*sc] addresses the fp32 master weight in either role (forward: down/up sampler,
 // backward: the same tensors transposed), so no transposed copy exists.   Reference: net_trans.py:629-643.
-#include <atomic>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "prims.h"
@@ -213,7 +212,7 @@ void gproj_narrow(const Ctx& ctx, const void* x, long rows, int C, int ds, int g
 // dx = BN backward of dy (bn_bwd_apply, no ReLU), y = dx (x)_g W -- one pass (gproj_narrow_k<BNB>)
 void gproj_narrow_bnb(const Ctx& ctx, const void* dy, const void* xv, void* dx, long rows, int C, int ds, int g, const float* W, long sg,
                       long sj, long sc, void* y, const float* mean, const float* rstd, const float* bsc, const float* bsh, const float* sums, int training) {
-  if (!rowfuse_mode(-1)) {
+  if (!tune(T_ROWFUSE)) {
     bn_bwd_apply(ctx, dy, xv, dx, rows, C, mean, rstd, bsc, bsh, sums, 0, 1, training);
     gproj_narrow(ctx, dx, rows, C, ds, g, W, sg, sj, sc, y);
     return;
@@ -415,16 +414,9 @@ __global__ __launch_bounds__(256, PROJ_DG > 8 ? 2 : 3) void modln_gproj_k(const 
   }
 }
 
-int rowfuse_mode(int set) {                              // -1: query; 0 / 1: off / on (DGSCT_NO_ROWFUSE=1 starts it off); returns the old value
-  static std::atomic<int> mode{(getenv("DGSCT_NO_ROWFUSE") && atoi(getenv("DGSCT_NO_ROWFUSE"))) ? 0 : 1};
-  const int old = mode.load(std::memory_order_relaxed);
-  if (set >= 0) mode.store(set ? 1 : 0, std::memory_order_relaxed);
-  return old;
-}
-
 bool modln_gproj_supported(int mode, int C, int ds, int g) {
   ProjGeom pg;
-  return rowfuse_mode(-1) && gproj_supported(mode, C, ds, g) && proj_geom(mode, C, ds, g, 1 << 20, 1024, pg) && (pg.gs == 16 || pg.gs == 32);   // (DGSCT_NO_GPROJ switches this pass off too)
+  return tune(T_ROWFUSE) && gproj_supported(mode, C, ds, g) && proj_geom(mode, C, ds, g, 1 << 20, 1024, pg) && (pg.gs == 16 || pg.gs == 32);   // (DGSCT_NO_GPROJ switches this pass off too)
 }
 
 void modln_gproj(const Ctx& ctx, const void* X1, const float* ch, const float* sg, const float* tg, float alpha, float beta, float gamma,

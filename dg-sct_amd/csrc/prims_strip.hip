@@ -10,8 +10,6 @@
 // channel per workgroup.  The UNR loads of a trip are UNCONDITIONAL (tail rows read a clamped, valid row and are
 // masked afterwards): a per-row "load or zero" makes hipcc branch around each load and emit s_waitcnt vmcnt(0)
 // after every one of them, i.e. four serial HBM round trips instead of four loads in flight.
-#include <atomic>
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "prims.h"
 #include "device_util.h"
@@ -67,7 +65,6 @@ static inline int col_ve(const Ctx& ctx, int C) {
     else fn_ = (VE_) == 4 ? reinterpret_cast<const void*>(&KERNEL<DT_F32, 4>)                                \
                           : reinterpret_cast<const void*>(&KERNEL<DT_F32, 1>);                               \
     OUT = wg_capacity(fn_, SHMEM);                                                                          \
-    if (const char* e_ = getenv("DGSCT_COL_CAP")) { if (atoi(e_) > 0) OUT = atoi(e_); }                       \
   } while (0)
 #define COL_DISPATCH(ctx, VE_, KERNEL, GRID, SHMEM, ...)                                                   \
   do {                                                                                                      \
@@ -116,11 +113,7 @@ __device__ __forceinline__ void flush_strip(float (&acc)[NQ][VE], float* lds, in
   __syncthreads();
 }
 // un-batched pure streams too are launched as ONE round of resident workgroups (bn_bwd_apply at 368 640 x 128: 2880
-// workgroups on 768 slots, 102 -> 70 us; per-frame grids (scale_cols) gain nothing: the frame count quantises them).  DGSCT_COL_STREAM_CAP=0 restores the fixed ~4096-workgroup target.
-static inline bool stream_cap() {
-  static const bool on = !(getenv("DGSCT_COL_STREAM_CAP") && atoi(getenv("DGSCT_COL_STREAM_CAP")) == 0);
-  return on;
-}
+// workgroups on 768 slots, 102 -> 70 us; per-frame grids (scale_cols) gain nothing: the frame count quantises them).
 static inline size_t strip_lds(int C, int ve) {
   const int nvr = C / ve, tpr = nvr < 256 ? nvr : 256;
   return (size_t)(256 / tpr) * C * sizeof(float);
@@ -383,30 +376,25 @@ __global__ __launch_bounds__(256) void affine_act_bn_k(const void* x, void* y, l
   }
 }
 
-int bnfold_mode(int set) {
-  static std::atomic<int> mode{getenv("DGSCT_NO_BNFOLD") ? 0 : 1};
-  const int old = mode.load(std::memory_order_relaxed);
-  if (set >= 0) mode.store(set ? 1 : 0, std::memory_order_relaxed);
-  return old;
-}
-
 void affine_act_bn(const Ctx& ctx, const void* x, void* y, long rows, int C, const BnFin& fin, int relu) {
-  if (!bnfold_mode(-1) || rows < 1) {
+  if (!tune(T_BNFOLD) || rows < 1) {
     bn_finalize(ctx, fin.acc, fin.rows, C, fin.w, fin.b, fin.run_mean, fin.run_var, fin.momentum, fin.eps, fin.training, fin.mean,
                 fin.rstd, fin.sc, fin.sh);
     affine_act(ctx, x, y, rows, C, fin.sc, fin.sh, relu);
     return;
   }
   const int ve = col_ve(ctx, C);
-  ColGeom g = col_geom(UNR1, C, ve, rows, 1);
-  if (stream_cap()) { int cap = 4096; COL_CAPACITY(cap, ctx, ve, affine_act_bn_k, 0); g = col_geom(UNR1, C, ve, rows, 1, cap, true); }
+  int cap = 4096;
+  COL_CAPACITY(cap, ctx, ve, affine_act_bn_k, 0);
+  const ColGeom g = col_geom(UNR1, C, ve, rows, 1, cap, true);
   COL_DISPATCH(ctx, ve, affine_act_bn_k, dim3(g.chunks), 0, x, y, rows, C, g.tpr, g.rpp, g.rpc, fin, relu);
 }
 
 void affine_act(const Ctx& ctx, const void* x, void* y, long rows, int C, const float* sc, const float* sh, int relu) {
   const int ve = col_ve(ctx, C);
-  ColGeom g = col_geom(UNR1, C, ve, rows, 1);
-  if (stream_cap()) { int cap = 4096; COL_CAPACITY(cap, ctx, ve, affine_act_k, 0); g = col_geom(UNR1, C, ve, rows, 1, cap, true); }
+  int cap = 4096;
+  COL_CAPACITY(cap, ctx, ve, affine_act_k, 0);
+  const ColGeom g = col_geom(UNR1, C, ve, rows, 1, cap, true);
   COL_DISPATCH(ctx, ve, affine_act_k, dim3(g.chunks), 0, x, y, rows, C, g.tpr, g.rpp, g.rpc, sc, sh, relu);
 }
 
@@ -459,20 +447,13 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_k(const void* dy, const void
   }
 }
 
-static inline long strip_part_min() {      // tuning hook: below this many atomics the extra finishing launch costs more (A/B: tools/ab_partmin.sh)
-  static const long v = getenv("DGSCT_STRIP_PART_MIN") ? atol(getenv("DGSCT_STRIP_PART_MIN")) : 150000;
-  return v;
-}
-static inline bool strip_part() {
-  static const bool on = !(getenv("DGSCT_ROW_PART") && atoi(getenv("DGSCT_ROW_PART")) == 0);
-  return on;
-}
+constexpr long STRIP_PART_MIN = 150000;      // below this many atomics the extra finishing launch costs more
 void bn_bwd_stats(const Ctx& ctx, const void* dy, const void* x, long rows, int C, const float* mean, const float* rstd,
                   const float* sc, const float* sh, int relu, float* sums, float* part, long part_floats) {
   const int ve = col_ve(ctx, C);
   ColGeom g = col_geom(UNR2, C, ve, rows, 1, 768);
   // (workgroups x channels of atomics below ~150 k cost less than the finishing launch: measured 9.9 -> 9.0 + 4.7 us)
-  if (!strip_part() || (long)g.chunks * 2 * C > part_floats || (long)g.chunks * 2 * C < strip_part_min()) part = nullptr;
+  if ((long)g.chunks * 2 * C > part_floats || (long)g.chunks * 2 * C < STRIP_PART_MIN) part = nullptr;
   COL_DISPATCH(ctx, ve, bn_bwd_stats_k, dim3(g.chunks), strip_lds(C, ve), dy, x, rows, C, mean, rstd, sc, sh, relu,
                g.tpr, g.rpp, g.rpc, sums, part);
   if (part) {
@@ -534,8 +515,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const void* dy, const void
 void bn_bwd_apply(const Ctx& ctx, const void* dy, const void* x, void* dx, long rows, int C, const float* mean,
                   const float* rstd, const float* sc, const float* sh, const float* sums, int relu, int has_bn, int training) {
   const int ve = col_ve(ctx, C);
-  ColGeom g = col_geom(UNR2, C, ve, rows, 1);
-  if (stream_cap()) { int cap = 4096; COL_CAPACITY(cap, ctx, ve, bn_bwd_apply_k, 0); g = col_geom(UNR2, C, ve, rows, 1, cap, true); }
+  int cap = 4096;
+  COL_CAPACITY(cap, ctx, ve, bn_bwd_apply_k, 0);
+  const ColGeom g = col_geom(UNR2, C, ve, rows, 1, cap, true);
   COL_DISPATCH(ctx, ve, bn_bwd_apply_k, dim3(g.chunks), 0, dy, x, dx, rows, C, g.tpr, g.rpp, g.rpc, mean, rstd, sc, sh, sums,
                relu, has_bn, training);
 }
@@ -668,7 +650,7 @@ void relu_bwd_scale(const Ctx& ctx, const void* x, void* y, int B, int N, int C,
   if (colsum_out) COL_CAPACITY(cap, ctx, ve, relu_bwd_scale_k, strip_lds(C, ve));
   ColGeom g = col_geom(UNR1, C, ve, N, B, cap, colsum_out != nullptr);
   // partial sums pay from ~150 k atomics up (480 workgroups x 512 channels: 26.1 -> 16.4 + 4.7 us; x 128 channels: no gain)
-  if (!colsum_out || !strip_part() || (long)g.chunks * B * C > part_floats || (long)g.chunks * B * C < strip_part_min()) part = nullptr;
+  if (!colsum_out || (long)g.chunks * B * C > part_floats || (long)g.chunks * B * C < STRIP_PART_MIN) part = nullptr;
   COL_DISPATCH(ctx, ve, relu_bwd_scale_k, dim3(g.chunks, B), strip_lds(C, ve), x, y, N, C, g.tpr, g.rpp, g.rpc, roww,
                colw, cdt, colw2, scale, colsum_out, part);
   if (part) {

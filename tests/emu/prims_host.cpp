@@ -34,7 +34,6 @@ void gemm_prof_collect(long* n, double* ms, double* fl) { if (n) *n = 0; if (ms)
 void* stream_create(int) { return nullptr; }
 void stream_destroy(void*) {}
 void stream_fork(const Ctx&) {}
-int call_prof_mode(int) { return 0; }
 void* call_prof_begin(void*, int, int, int) { return nullptr; }
 void call_prof_end(void*) {}
 void call_prof_dump(const char*) {}
@@ -44,10 +43,7 @@ void event_record(const Ctx&, void*) {}
 void event_wait(const Ctx&, void*) {}
 void check_async(const char*) {}
 void clear_async() {}
-int gemm_skinny_mode(int) { return 0; }
-static int g_wgbt = 1;
-int wgrad_bt_mode(int set) { const int old = g_wgbt; if (set >= 0) g_wgbt = set ? 1 : 0; return old; }
-bool wgrad_bt_supported(const Ctx&, const WgBtJob*, int n) { return g_wgbt && n >= 1 && n <= WGBT_MAX; }
+bool wgrad_bt_supported(const Ctx&, const WgBtJob*, int n) { return tune(T_WGBT) && n >= 1 && n <= WGBT_MAX; }
 void wgrad_bt(const Ctx& ctx, const WgBtJob* jobs, int n) {          // (either element type: the host loops read through ld())
   for (int i = 0; i < n; ++i) {
     const WgBtJob& j = jobs[i];
@@ -59,10 +55,6 @@ void wgrad_bt(const Ctx& ctx, const WgBtJob* jobs, int n) {          // (either 
       }
   }
 }
-int gemm_tall_mode(int) { return 0; }
-int gemm8_mode(int) { return 0; }                 // (the 8-wave GEMM kernel is a device-side choice: nothing to emulate)
-int gemm_noatomic_mode(int) { return 0; }
-int gemm8_stag_mode(int) { return 0; }
 
 void zero(const Ctx&, void* p, size_t bytes) { if (bytes) std::memset(p, 0, bytes); }
 
@@ -133,10 +125,8 @@ void gemm(const Ctx& ctx, const Gemm& g) {
       }
 }
 
-static int g_vq1fuse = 1;
-int vq1fuse_mode(int set) { const int old = g_vq1fuse; if (set >= 0) g_vq1fuse = set > 2 ? 1 : set; return old; }
 bool vq1_fused_shape(int, int, int) { return true; }                   // (host loops: any shape, either element type)
-bool vq1_fused_supported(int, int, int) { return g_vq1fuse != 0; }
+bool vq1_fused_supported(int, int, int) { return tune(T_VQ1FUSE) != 0; }
 void vq1sum_fwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, int B, int N, int C, float invN, float* msum, void* vq1) {
   const int E = ctx.mode;
   for (int b = 0; b < B; ++b)
@@ -176,9 +166,7 @@ void vq1_bwd(const Ctx& ctx, const void* X1, const void* Wv1, const float* bv1, 
     }
 }
 
-static int g_skfuse = 1;
-int skfuse_mode(int set) { const int old = g_skfuse; if (set >= 0) g_skfuse = set ? 1 : 0; return old; }
-bool skinny_fused_supported(const Ctx&, int M, int, int, int) { return g_skfuse && M <= 256; }   // (host loops: any width, either element type)
+bool skinny_fused_supported(const Ctx&, int M, int, int, int) { return tune(T_SKFUSE) && M <= 256; }   // (host loops: any width, either element type)
 void skinny_fused(const Ctx& ctx, const SkFuse& p) {
   const int E = ctx.mode;
   std::vector<float> a((size_t)p.M * p.K);
@@ -267,10 +255,11 @@ void colsum_batched_pos(const Ctx& ctx, const void* x, long ldx, long bs, int B,
 }
 
 // ---- fused GEMM hooks (csrc/gemm_fx.hip): the same math in host loops, either element type, either B layout ------------------------
-static int g_gemmfx = 31 + 64 + 128;      // (all call sites, prologues at every width: the host loops have no tile economics)
-int gemmfx_mode(int set) { const int old = g_gemmfx; if (set >= 0) g_gemmfx = set & 255; return old; }
+// The emulation's one deliberate difference from the device's switch table: all call sites, prologues at every width (bit 16) --
+// the host loops have no tile economics.  Set once at load.
+static const int g_gemmfx_at_load = tune_set(T_GEMMFX, 31 + 64 + 128);
 bool gemm_fx_supported(const Ctx&, const Gemm& g, const GemmFx& fx) {
-  if (!g_gemmfx || !g.A.kmajor || g.KB != 1 || g.atomic) return false;
+  if (!tune(T_GEMMFX) || !g.A.kmajor || g.KB != 1 || g.atomic) return false;
   const bool frames = fx.a_pro == APRO_MASKSCALE || fx.epi == EPI_XCBWD || fx.epi == EPI_COLSUM;
   if (frames && (fx.rpf <= 0 || g.batch != 1 || g.M % fx.rpf)) return false;
   return true;
@@ -544,9 +533,7 @@ void gproj_narrow(const Ctx& ctx, const void* x, long rows, int C, int ds, int g
         st(y, ctx.mode, r * ds + gi * dg + jl, (float)s);
       }
 }
-static int g_rowfuse = 1;
-int rowfuse_mode(int set) { const int old = g_rowfuse; if (set >= 0) g_rowfuse = set ? 1 : 0; return old; }
-bool modln_gproj_supported(int mode, int C, int ds, int g) { return g_rowfuse && gproj_supported(mode, C, ds, g); }
+bool modln_gproj_supported(int mode, int C, int ds, int g) { return tune(T_ROWFUSE) && gproj_supported(mode, C, ds, g); }
 
 void modln_gproj(const Ctx& ctx, const void* X1, const float* ch, const float* sg, const float* tg, float alpha, float beta, float gamma,
                  const float* lnw, const float* lnb, float eps, int B, int N, int C, int ds, int g, const float* W, long wsg, long wsj,
@@ -557,9 +544,7 @@ void modln_gproj(const Ctx& ctx, const void* X1, const float* ch, const float* s
 }
 
 // ---- fused gate / bottleneck passes (csrc/fused_gate.hip): host loops with the same rounding points (stored tensors rounded to E)
-static int g_gatefuse = 1;
-int gatefuse_mode(int set) { const int old = g_gatefuse; if (set >= 0) g_gatefuse = set ? 1 : 0; return old; }
-bool gate_fused_supported(int, int, int, int ds, int g) { return g_gatefuse && ds % g == 0; }      // the emulation takes every shape
+bool gate_fused_supported(int, int, int, int ds, int g) { return tune(T_GATEFUSE) && ds % g == 0; }      // the emulation takes every shape
 void gatemod_fwd(const Ctx& ctx, const void* X1, const float* ch, const void* aq2, const float* Wv2, const float* bv2, const float* ws,
                  const float* bs, const float* tg, float alpha, float beta, float gamma, const float* lnw, const float* lnb, float eps,
                  int B, int N, int C, int ds, int g, const float* Wd, float* sl, void* X3, float* mu, float* rstd, void* Zp,
@@ -680,8 +665,6 @@ void bn_finalize(const Ctx&, const float* acc, long rows, int C, const float* w,
   }
 }
 
-static int g_bnfold = 1;
-int bnfold_mode(int set) { const int old = g_bnfold; if (set >= 0) g_bnfold = set ? 1 : 0; return old; }
 void affine_act(const Ctx& ctx, const void* x, void* y, long rows, int C, const float* sc, const float* sh, int relu);
 void affine_act_bn(const Ctx& ctx, const void* x, void* y, long rows, int C, const BnFin& f, int relu) {
   bn_finalize(ctx, f.acc, f.rows, C, f.w, f.b, f.run_mean, f.run_var, f.momentum, f.eps, f.training, f.mean, f.rstd, f.sc, f.sh);

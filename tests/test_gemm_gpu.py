@@ -359,6 +359,24 @@ def test_gemm_skinny_is_actually_used():
         lib.prof_enable(False)
 
 
+def test_tune_defaults_and_retired_environment_switches():
+    """the real library's switch table (csrc/tune.h) answers the literal defaults -- gemmfx: 15 + 64 + 128 = 207, the fused-engine call
+    sites the default schedule has always taken (bit 16, the prologues at every width, is on in the host emulation only) -- and a
+    fresh process that sets three of the retired DGSCT_NO_* / DGSCT_G8STAG variables gets the same answers: they are no longer read.
+    The child loads the library and launches nothing."""
+    import os, subprocess, sys
+    lib = default_lib()
+    on = ("gemm8", "g8stag", "wgbt", "skinny", "gemmtall", "vq1fuse", "gatefuse", "rowfuse", "bnfold", "skfuse")
+    for key in on:
+        assert lib.test_tune(key, -1) == 1, key
+    assert lib.test_tune("gemmfx", -1) == 207
+    assert lib.test_tune("callprof", -1) == 0
+    code = ("import ctypes; c = ctypes.CDLL(%r); print(*[c.dgsct_test_tune(k, -1) for k in (b'gatefuse', b'bnfold', b'g8stag')])" % lib.path)
+    env = dict(os.environ, DGSCT_NO_GATEFUSE="1", DGSCT_NO_BNFOLD="0", DGSCT_G8STAG="0")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout.split()
+    assert out == ["1", "1", "1"]
+
+
 # ---- gemm_tall.hip: weight gradients over the token rows (both operands [rows][width], small output, very deep contraction) ----------
 @pytest.mark.parametrize("M,N,pad", [(96, 96, 0), (128, 128, 0), (48, 96, 0), (8, 48, 4), (48, 8, 4), (96, 128, 0), (12, 192, 0), (32, 256, 0), (72, 120, 0)])
 def test_gemm_tall_weight_gradients(M, N, pad):
