@@ -149,6 +149,14 @@ class Lib:
             self._logmel_scratch.restype = C.c_int64
         if self._patch_embed is not None:
             self._patch_embed.argtypes = [C.c_int] * 9 + [C.c_void_p] * 7 + [C.c_float] + [C.c_void_p] * 2
+        # optional (include/dgsct.h): the parameter gradients of the patch embedding, for a trainable front end
+        self._patch_embed_pws = getattr(c, "dgsct_patch_embed_params_ws_floats", None)
+        self._patch_embed_bwd_params = getattr(c, "dgsct_patch_embed_backward_params", None)
+        if self._patch_embed_pws is not None:
+            self._patch_embed_pws.argtypes = [C.c_int] * 6
+            self._patch_embed_pws.restype = C.c_int64
+        if self._patch_embed_bwd_params is not None:
+            self._patch_embed_bwd_params.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8 + [C.c_float] + [C.c_void_p] * 8
         # optional (include/dgsct.h): patch merging between two stages (csrc/pmerge.hip); the host emulation lacks it
         self._pmerge_ws = getattr(c, "dgsct_patch_merge_ws_bytes", None)
         self._pmerge_fwd = getattr(c, "dgsct_patch_merge_forward", None)
@@ -280,6 +288,25 @@ class Lib:
         self._check(self._front_end(self._patch_embed, "dgsct_patch_embed_forward")(mode, in_dtype, out_dtype, B, in_chans, H, W, T, C_, x,
                                                                                      bn_scale, bn_shift, w, b, ln_w, ln_b, eps, out, stream),
                     "dgsct_patch_embed_forward")
+
+    def has_patch_embed_params(self) -> bool:
+        """whether this library exports dgsct_patch_embed_backward_params / dgsct_patch_embed_params_ws_floats (the gradients of
+        `patch_embed.*` and `bn0.*`, for a trainable front end) on top of dgsct_patch_embed_forward"""
+        return None not in (self._patch_embed, self._patch_embed_pws, self._patch_embed_bwd_params)
+
+    def patch_embed_params_ws_floats(self, mode: int, B: int, in_chans: int, H: int, W: int, C_: int) -> int:
+        n = self._front_end(self._patch_embed_pws, "dgsct_patch_embed_params_ws_floats")(mode, B, in_chans, H, W, C_)
+        if n < 0:
+            raise RuntimeError(f"dgsct_patch_embed_params_ws_floats failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def patch_embed_backward_params(self, mode, in_dtype, dout_dtype, B, in_chans, H, W, T, C_, x, bn_scale, bn_shift, bn_pivot, w, b, ln_w, ln_b,
+                                    eps, dout, dw, db, dln_w, dln_b, dbn, ws, stream):
+        """dw [C, in_chans, 4, 4], db / dln_w / dln_b [C], audio mode: dbn [2, 64] = (g1, g0); all fp32 and all written by the call
+        (include/dgsct.h: dgsct_patch_embed_backward_params)"""
+        self._check(self._front_end(self._patch_embed_bwd_params, "dgsct_patch_embed_backward_params")(
+            mode, in_dtype, dout_dtype, B, in_chans, H, W, T, C_, x, bn_scale, bn_shift, bn_pivot, w, b, ln_w, ln_b, eps, dout, dw, db, dln_w,
+            dln_b, dbn, ws, stream), "dgsct_patch_embed_backward_params")
 
     @property
     def has_patch_merge(self) -> bool:

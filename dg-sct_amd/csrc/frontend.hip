@@ -1,5 +1,6 @@
 // Audio and image front ends (the part in front of the first block): what turns a waveform / an image into the
-// patch tokens the backbone blocks consume.  Forward only: both inputs are data and both sub-modules are frozen.
+// patch tokens the backbone blocks consume.  Both inputs are data: no kernel here returns an input gradient.  The sub-modules are frozen
+// in every AVE / AVVP configuration; AVS-S4 trains `bn0` and `patch_embed`, and patch_embed_bwd_k returns their gradients.
 //
 //   logmel_k       waveform [B][L] -> log-mel [B][T][64], T = L / 320 + 1.  Replaces `spectrogram_extractor` + `logmel_extractor`
 //                  (DG-SCT/AVE/nets/net_trans.py:857-858; htsat.py:443-449): reflect padding, periodic Hann window, 1024-point DFT,
@@ -16,6 +17,11 @@
 //                  tokens at a time: its 64 lanes fetch the 4 x 16 pixels of the four patches (per channel), every lane owns the
 //                  embedding channels lane, lane + 64, lane + 128, pixels reach all lanes through v_readlane, the [K][C] weights sit
 //                  in LDS (read conflict-free: consecutive lanes, consecutive channels).
+//   patch_embed_bwd_k      gradients of proj.weight / proj.bias / norm.weight / norm.bias and, in audio mode, the two sums per mel bin that
+//                  give d bn0.weight / d bn0.bias, from dOut (fp32 | bf16), all in fp32.  The forward's ownership and address arithmetic;
+//                  the convolution and the LayerNorm statistics are recomputed from x (the forward stores nothing for it), the sums stay in
+//                  registers across the grid-stride loop, the four waves meet in LDS, each workgroup stores one partial row and
+//                  patch_embed_bwd_sum_k adds the rows in a fixed order: no atomics, bit-identical from call to call.
 //
 // The extern "C" entry points live here (not in capi.cpp): the host emulation of the CPU tests links capi.cpp against host
 // primitives and has no front end.
@@ -190,6 +196,47 @@ __device__ __forceinline__ void fe_cubic(float t, float (&c)[4]) {
   c[3] = ((A * d - 5.f * A) * d + 8.f * A) * d - 4.f * A;
 }
 
+// The pixels (row r, column dx) of token `tok`, one per input channel, as the convolution sees them (0 past the last token).  Audio mode:
+// the bicubic stretch and the fold are the address arithmetic, `bn0` the scale / shift; `raw` is the stretched log-mel before `bn0` and
+// f its mel bin (what the `bn0` gradients are collected over).
+template <int IC, bool AUDIO>
+__device__ __forceinline__ void fe_pixels(const PatchArgs& p, long tok, int r, int dx, float (&v)[IC], float& raw, int& f) {
+  const long P = (long)p.Hp * p.Wp;
+#pragma unroll
+  for (int ch = 0; ch < IC; ++ch) v[ch] = 0.f;
+  raw = 0.f; f = 0;
+  if (tok < p.tokens) {
+    const long b = tok / P;
+    const int pi = (int)(tok - b * P), pr = pi / p.Wp, pc = pi - pr * p.Wp;
+    if (AUDIO) {
+      f = 4 * (pr & 15) + r;
+      const int tp = (pr >> 4) * 256 + 4 * pc + dx;                              // image[q*64 + f][t'] = logmel'[q*256 + t'][f]
+      const float* lm = reinterpret_cast<const float*>(p.x) + b * (long)p.T * FE_NMEL + f;
+      float val;
+      if (p.T == FE_MAX_T) val = lm[(long)tp * FE_NMEL];
+      else {
+        const float src = p.tscale * (float)tp, fl = floorf(src);
+        const int i0 = (int)fl;
+        float cf[4];
+        fe_cubic(src - fl, cf);
+        val = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          int ii = i0 - 1 + e;
+          ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
+          val += cf[e] * lm[(long)ii * FE_NMEL];
+        }
+      }
+      raw = val;
+      v[0] = val * p.bn_scale[f] + p.bn_shift[f];
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < IC; ++ch)
+        v[ch] = lde_rt(p.x, p.xdt, ((b * IC + ch) * p.H + 4 * pr + r) * (long)p.W + 4 * pc + dx);
+    }
+  }
+}
+
 template <int IC, bool AUDIO, int NJ>
 __global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
   constexpr int K = IC * 16;
@@ -211,41 +258,13 @@ __global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
   }
   __syncthreads();
   const int r = lane >> 4, tt = (lane >> 2) & 3, dx = lane & 3;      // this lane's pixel: row r, column dx of token tt of the group
-  const long P = (long)p.Hp * p.Wp, ngroups = (p.tokens + 3) >> 2;
+  const long ngroups = (p.tokens + 3) >> 2;
   const float invC = 1.f / (float)C;
   for (long grp = (long)blockIdx.x * 4 + (threadIdx.x >> 6); grp < ngroups; grp += (long)gridDim.x * 4) {
     const long tok0 = grp * 4, tok = tok0 + tt;
-    float v[IC];
-#pragma unroll
-    for (int ch = 0; ch < IC; ++ch) v[ch] = 0.f;
-    if (tok < p.tokens) {
-      const long b = tok / P;
-      const int pi = (int)(tok - b * P), pr = pi / p.Wp, pc = pi - pr * p.Wp;
-      if (AUDIO) {
-        const int f = 4 * (pr & 15) + r, tp = (pr >> 4) * 256 + 4 * pc + dx;     // image[q*64 + f][t'] = logmel'[q*256 + t'][f]
-        const float* lm = reinterpret_cast<const float*>(p.x) + b * (long)p.T * FE_NMEL + f;
-        float val;
-        if (p.T == FE_MAX_T) val = lm[(long)tp * FE_NMEL];
-        else {
-          const float src = p.tscale * (float)tp, fl = floorf(src);
-          const int i0 = (int)fl;
-          float cf[4];
-          fe_cubic(src - fl, cf);
-          val = 0.f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            int ii = i0 - 1 + e;
-            ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
-            val += cf[e] * lm[(long)ii * FE_NMEL];
-          }
-        }
-        v[0] = val * p.bn_scale[f] + p.bn_shift[f];
-      } else {
-#pragma unroll
-        for (int ch = 0; ch < IC; ++ch)
-          v[ch] = lde_rt(p.x, p.xdt, ((b * IC + ch) * p.H + 4 * pr + r) * (long)p.W + 4 * pc + dx);
-      }
-    }
+    float v[IC], raw;
+    int f;
+    fe_pixels<IC, AUDIO>(p, tok, r, dx, v, raw, f);
     float acc[4][NJ];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -298,6 +317,252 @@ static void patch_embed_nj(const PatchArgs& a, hipStream_t s) {
   else patch_embed_launch<IC, AUDIO, 3>(a, s);
 }
 
+// ---- patch embedding: parameter gradients ------------------------------------------------------------------------------------------
+constexpr int PE_BWD_MAX_WG = 1024;       // rows of the workspace: one partial row per workgroup, summed by patch_embed_bwd_sum_k
+
+struct PatchBwdArgs {
+  PatchArgs f;                             // the forward's operands (out / odt / ln_b unused)
+  const void* dout; int ddt;               // [B][Hp * Wp][C] fp32 | bf16
+  const float* pivot;                      // audio: [64], what the `bn0` sums are centred on (the mean `bn0` used)
+  float* ws; int rs;                       // [gridDim.x][rs], rs = (K + 3) C (+ 128 in audio mode)
+};
+
+// Gradients of proj.weight / proj.bias / norm.weight / norm.bias (and the two `bn0` sums in audio mode) from dOut, with the forward's
+// ownership: one wavefront per four tokens, a lane owns the channels lane, lane + 64, lane + 128 and fetches one pixel of the group.  Per
+// group: the convolution and the LayerNorm statistics are recomputed from x (nothing token-sized is read but x and dOut), then per token
+//   yh = (conv - mean) rstd,  d norm.weight += dOut yh,  d norm.bias += dOut,  dy = dOut norm.weight,
+//   dconv = rstd (dy - mean_c(dy) - yh mean_c(dy yh)),   d proj.bias += dconv,   d proj.weight[c][k] += dconv[c] pix[k].
+// Audio mode: with dpix = W^T dconv, g1[f] = sum dpix (S(lm) - pivot[f]) and g0[f] = sum dpix per mel bin f.  The four tokens of a group
+// share their patch row, so f = 4 (pr & 15) + r depends on the pixel row r alone: a lane forms, per row and over its own channels,
+// sum_c dconv[c] sum_dx W[4r + dx][c] s[r][dx] and sum_c dconv[c] sum_dx W[4r + dx][c], the wave sums those eight numbers once per group and
+// adds them to its 2 x 64 bins in LDS.  Everything else stays in registers across the grid-stride loop; at the end the four waves add
+// their registers into one [K + 3][C] LDS buffer one after the other (a fixed order) and the workgroup stores ONE row of the workspace.
+// No atomics: the result depends on the grid alone.
+template <int IC, bool AUDIO, int NJ>
+__global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
+  constexpr int K = IC * 16, KR = K + 3;
+  __shared__ float sm[KR * NJ * 64];               // the weights [k][c] at pitch C during the loop, the combined sums [K + 3][C] after it
+  __shared__ float bins[AUDIO ? 4 * 128 : 1];      // [wave][g1 | g0][mel bin]
+  const PatchArgs& p = a.f;
+  const int C = p.C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < K * C; i += 256) {
+    const int c = i / K, k = i - c * K;
+    sm[k * C + c] = p.w[i];
+  }
+  if (AUDIO)
+    for (int i = threadIdx.x; i < 4 * 128; i += 256) bins[i] = 0.f;
+  float bias[NJ], lw[NJ];
+  int cw[NJ];                                      // this lane's channels, clamped for the reads (lanes past C carry zeros)
+  bool cv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = lane + 64 * j;
+    cv[j] = c < C;
+    cw[j] = cv[j] ? c : C - 1;
+    bias[j] = p.bias[cw[j]]; lw[j] = p.ln_w[cw[j]];
+  }
+  __syncthreads();
+  float wrow[4][NJ];                               // audio: sum_dx W[4r + dx][c]
+  if (AUDIO) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        wrow[rr][j] = (sm[(4 * rr) * C + cw[j]] + sm[(4 * rr + 1) * C + cw[j]]) + (sm[(4 * rr + 2) * C + cw[j]] + sm[(4 * rr + 3) * C + cw[j]]);
+  }
+  float dW[K][NJ], db[NJ], dlw[NJ], dlb[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    db[j] = 0.f; dlw[j] = 0.f; dlb[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) dW[k][j] = 0.f;
+  }
+  const int r = lane >> 4, tt = (lane >> 2) & 3, dx = lane & 3;      // this lane's pixel: row r, column dx of token tt of the group
+  const long ngroups = (p.tokens + 3) >> 2;
+  const float invC = 1.f / (float)C;
+  for (long grp = (long)blockIdx.x * 4 + wave; grp < ngroups; grp += (long)gridDim.x * 4) {
+    const long tok0 = grp * 4;
+    float v[IC], raw;
+    int f;
+    fe_pixels<IC, AUDIO>(p, tok0 + tt, r, dx, v, raw, f);
+    const float sv = AUDIO ? raw - a.pivot[f] : 0.f;
+    float g[4][NJ];                                // dOut of the four tokens, in flight while the convolution is recomputed
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        g[t][j] = (cv[j] && tok0 + t < p.tokens) ? lde_rt(a.dout, a.ddt, (tok0 + t) * C + lane + 64 * j) : 0.f;
+    float acc[4][NJ];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[t][j] = bias[j];
+#pragma unroll
+    for (int ch = 0; ch < IC; ++ch)
+#pragma unroll
+      for (int rd = 0; rd < 16; ++rd) {            // rd = row * 4 + column inside the patch
+        float w[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) w[j] = sm[(ch * 16 + rd) * C + cw[j]];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float xv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[ch]), (rd >> 2) * 16 + t * 4 + (rd & 3)));
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[t][j] += xv * w[j];
+        }
+      }
+    // LayerNorm backward per token: acc becomes dconv (0 in the lanes past C and for the tokens past the last one)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (tok0 + t < p.tokens) {                   // wave-uniform
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) s += cv[j] ? acc[t][j] : 0.f;
+        const float mean = group_sum(s, 64) * invC;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { acc[t][j] -= mean; q += cv[j] ? acc[t][j] * acc[t][j] : 0.f; }
+        const float rstd = 1.f / sqrtf(group_sum(q, 64) * invC + p.eps);
+        float dy[NJ], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          acc[t][j] *= rstd;                       // yh
+          dlw[j] += g[t][j] * acc[t][j]; dlb[j] += g[t][j];
+          dy[j] = g[t][j] * lw[j];                 // (g is 0 in the lanes past C)
+          s1 += dy[j]; s2 += dy[j] * acc[t][j];
+        }
+        group_sum2(s1, s2, 64);
+        const float m1 = s1 * invC, m2 = s2 * invC;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          acc[t][j] = cv[j] ? rstd * (dy[j] - m1 - acc[t][j] * m2) : 0.f;
+          db[j] += acc[t][j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[t][j] = 0.f;
+      }
+    }
+    float p1[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ch = 0; ch < IC; ++ch)
+#pragma unroll
+      for (int rd = 0; rd < 16; ++rd) {
+        const int k = ch * 16 + rd;
+        float u[NJ];                               // audio: sum_t dconv[t][c] s[t][rd]
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) u[j] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int src = (rd >> 2) * 16 + t * 4 + (rd & 3);
+          const float xv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[ch]), src));
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) dW[k][j] += xv * acc[t][j];
+          if (AUDIO) {
+            const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sv), src));
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) u[j] += sx * acc[t][j];
+          }
+        }
+        if (AUDIO) {
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) p1[rd >> 2] += u[j] * sm[k * C + cw[j]];
+        }
+      }
+    if (AUDIO) {
+      float p0[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const float ds = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) p0[rr] += ds * wrow[rr][j];
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) group_sum2(p1[rr], p0[rr], 64);
+      if (lane < 8) {                              // lane = which * 4 + row: one bin each
+        const int rr = lane & 3;
+        const float a1 = rr == 0 ? p1[0] : rr == 1 ? p1[1] : rr == 2 ? p1[2] : p1[3];
+        const float a0 = rr == 0 ? p0[0] : rr == 1 ? p0[1] : rr == 2 ? p0[2] : p0[3];
+        const int pr = (int)(tok0 % ((long)p.Hp * p.Wp)) / p.Wp;     // the group's patch row (Wp = 64: four tokens never straddle two)
+        bins[wave * 128 + (lane >> 2) * 64 + 4 * (pr & 15) + rr] += lane < 4 ? a1 : a0;
+      }
+    }
+  }
+  // the four waves' registers into sm, one wave after the other
+  __syncthreads();                                 // every wave is done with the weights
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (cv[j]) {
+          const int c = lane + 64 * j;
+#pragma unroll
+          for (int k = 0; k < K; ++k) sm[k * C + c] = (w ? sm[k * C + c] : 0.f) + dW[k][j];
+          sm[K * C + c] = (w ? sm[K * C + c] : 0.f) + db[j];
+          sm[(K + 1) * C + c] = (w ? sm[(K + 1) * C + c] : 0.f) + dlw[j];
+          sm[(K + 2) * C + c] = (w ? sm[(K + 2) * C + c] : 0.f) + dlb[j];
+        }
+    }
+    __syncthreads();
+  }
+  float* row = a.ws + (long)blockIdx.x * a.rs;
+  for (int i = threadIdx.x; i < KR * C; i += 256) row[i] = sm[i];
+  if (AUDIO && threadIdx.x < 128)
+    row[KR * C + threadIdx.x] = (bins[threadIdx.x] + bins[128 + threadIdx.x]) + (bins[256 + threadIdx.x] + bins[384 + threadIdx.x]);
+}
+
+// column sums of the workspace in a fixed order: 16 columns x 16 row slices per workgroup, every slice summed in row order, the slices
+// in slice order.  Column k C + c goes to dweight[c][k] (the [C][IC][4][4] layout), the rest to dbias / dln_weight / dln_bias / dbn.
+__global__ __launch_bounds__(256) void patch_embed_bwd_sum_k(const float* __restrict__ ws, int rows, int rs, int K, int C, float* __restrict__ dw,
+                                                             float* __restrict__ db, float* __restrict__ dlw, float* __restrict__ dlb,
+                                                             float* __restrict__ dbn) {
+  __shared__ float red[16][17];
+  const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4, col = blockIdx.x * 16 + cl;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  if (col < rs) {
+    const float* q = ws + col;
+    int i = sl;
+    for (; i + 48 < rows; i += 64) {
+      const float v0 = q[(long)i * rs], v1 = q[(long)(i + 16) * rs], v2 = q[(long)(i + 32) * rs], v3 = q[(long)(i + 48) * rs];
+      s0 += v0; s1 += v1; s2 += v2; s3 += v3;
+    }
+    for (; i < rows; i += 16) s0 += q[(long)i * rs];
+  }
+  red[sl][cl] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  if (threadIdx.x < 16 && col < rs) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += red[i][cl];
+    const int KC = K * C;
+    if (col < KC) { const int k = col / C, c = col - k * C; dw[c * K + k] = s; }
+    else if (col < KC + C) db[col - KC] = s;
+    else if (col < KC + 2 * C) dlw[col - KC - C] = s;
+    else if (col < KC + 3 * C) dlb[col - KC - 2 * C] = s;
+    else dbn[col - KC - 3 * C] = s;
+  }
+}
+
+static long pe_bwd_rows(long tokens) {
+  const long want = ((tokens + 3) / 4 + 3) / 4;
+  return want < PE_BWD_MAX_WG ? want : PE_BWD_MAX_WG;
+}
+template <int IC, bool AUDIO, int NJ>
+static void patch_embed_bwd_launch(PatchBwdArgs& a, float* dw, float* db, float* dlw, float* dlb, float* dbn, hipStream_t s) {
+  const void* fn = reinterpret_cast<const void*>(&patch_embed_bwd_k<IC, AUDIO, NJ>);
+  const long rows = pe_bwd_rows(a.f.tokens), cap = wg_capacity(fn, 0);
+  const int grid = (int)(rows < cap ? rows : cap);                   // <= the rows the workspace holds
+  hipLaunchKernelGGL((patch_embed_bwd_k<IC, AUDIO, NJ>), dim3(grid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(patch_embed_bwd_sum_k, dim3((a.rs + 15) / 16), dim3(256), 0, s, (const float*)a.ws, grid, a.rs, IC * 16, a.f.C, dw, db, dlw, dlb, dbn);
+}
+template <int IC, bool AUDIO>
+static void patch_embed_bwd_nj(PatchBwdArgs& a, float* dw, float* db, float* dlw, float* dlb, float* dbn, hipStream_t s) {
+  const int nj = (a.f.C + 63) / 64;
+  if (nj == 1) patch_embed_bwd_launch<IC, AUDIO, 1>(a, dw, db, dlw, dlb, dbn, s);
+  else if (nj == 2) patch_embed_bwd_launch<IC, AUDIO, 2>(a, dw, db, dlw, dlb, dbn, s);
+  else patch_embed_bwd_launch<IC, AUDIO, 3>(a, dw, db, dlw, dlb, dbn, s);
+}
+
 static int fe_logmel_wgs(int B, int64_t L) {
   const int64_t T = L / FE_HOP + 1, npairs = (int64_t)B * ((T + 1) / 2);
   return (int)(npairs < FE_LOGMEL_MAX_WG ? npairs : FE_LOGMEL_MAX_WG);
@@ -313,6 +578,45 @@ static bool fe_logmel_check(const char* who, int B, int64_t L, int n_fft, int ho
   }
   return true;
 }
+
+// mode / shape limits shared by the forward, the parameter-gradient backward and its workspace size
+static bool fe_patch_geometry(const char* who, int mode, int B, int in_chans, int H, int W, int T, int C) {
+  if (B < 1 || C < 32 || C > 192 || C % 32) { set_error("%s: need B >= 1 and C a multiple of 32 up to 192 (got %d, %d)", who, B, C); return false; }
+  if (mode == DGSCT_PATCH_AUDIO) {
+    if (in_chans != 1 || H != 256 || W != 256 || T < 2 || T > FE_MAX_T) {
+      set_error("%s: audio mode takes an fp32 log-mel of 2 .. %d frames, bn scale / shift, in_chans = 1 and a 256 x 256 image", who, FE_MAX_T);
+      return false;
+    }
+  } else if (mode == DGSCT_PATCH_IMAGE) {
+    if ((in_chans != 1 && in_chans != 3) || H < 4 || W < 4 || H % 4 || W % 4) {
+      set_error("%s: image mode takes in_chans 1 or 3 and H, W multiples of 4 (got %d, %d x %d)", who, in_chans, H, W); return false;
+    }
+  } else { set_error("%s: unknown mode %d", who, mode); return false; }
+  const long tokens = (long)B * (H / 4) * (W / 4);
+  if (tokens * C > 0x7fffffffffLL || (long)B * in_chans * H * W > 0x7fffffffffLL) { set_error("%s: tensor too large", who); return false; }
+  return true;
+}
+// ... and the operands: fills `a` (everything but out / odt); tok_dtype = the dtype of the tokens (out) or of their gradient (dout)
+static bool fe_patch_check(const char* who, int mode, int in_dtype, int tok_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
+                           const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, const float* ln_weight,
+                           const float* ln_bias, float eps, PatchArgs& a) {
+  if (!x || !weight || !bias || !ln_weight || !ln_bias) { set_error("%s: NULL argument", who); return false; }
+  if ((tok_dtype != DGSCT_F32 && tok_dtype != DGSCT_BF16) || (in_dtype != DGSCT_F32 && in_dtype != DGSCT_BF16)) {
+    set_error("%s: dtypes must be DGSCT_F32 or DGSCT_BF16", who); return false;
+  }
+  if (mode == DGSCT_PATCH_AUDIO && (in_dtype != DGSCT_F32 || !bn_scale || !bn_shift)) {
+    set_error("%s: audio mode takes an fp32 log-mel of 2 .. %d frames, bn scale / shift, in_chans = 1 and a 256 x 256 image", who, FE_MAX_T);
+    return false;
+  }
+  if (!fe_patch_geometry(who, mode, B, in_chans, H, W, T, C)) return false;
+  a.x = x; a.xdt = in_dtype; a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.w = weight; a.bias = bias; a.ln_w = ln_weight; a.ln_b = ln_bias;
+  a.C = C; a.eps = eps;
+  if (mode == DGSCT_PATCH_AUDIO) { a.T = T; a.tscale = (float)(T - 1) / (float)(FE_MAX_T - 1); }
+  a.H = H; a.W = W; a.Hp = H / 4; a.Wp = W / 4;
+  a.tokens = (long)B * a.Hp * a.Wp;
+  return true;
+}
+static long pe_bwd_row_floats(int mode, int in_chans, int C) { return (long)(in_chans * 16 + 3) * C + (mode == DGSCT_PATCH_AUDIO ? 2 * FE_NMEL : 0); }
 
 }  // namespace dgsct
 
@@ -346,33 +650,43 @@ int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int 
                               const float* ln_bias, float eps, void* out, void* stream) {
   clear_error();
   const char* who = "dgsct_patch_embed_forward";
-  if (!x || !weight || !bias || !ln_weight || !ln_bias || !out) { set_error("%s: NULL argument", who); return 2; }
-  if ((out_dtype != DGSCT_F32 && out_dtype != DGSCT_BF16) || (in_dtype != DGSCT_F32 && in_dtype != DGSCT_BF16)) {
-    set_error("%s: dtypes must be DGSCT_F32 or DGSCT_BF16", who); return 2;
-  }
-  if (B < 1 || C < 32 || C > 192 || C % 32) { set_error("%s: need B >= 1 and C a multiple of 32 up to 192 (got %d, %d)", who, B, C); return 2; }
+  if (!out) { set_error("%s: NULL argument", who); return 2; }
   PatchArgs a{};
-  a.x = x; a.xdt = in_dtype; a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.w = weight; a.bias = bias; a.ln_w = ln_weight; a.ln_b = ln_bias;
-  a.out = out; a.odt = out_dtype; a.C = C; a.eps = eps;
-  if (mode == DGSCT_PATCH_AUDIO) {
-    if (in_chans != 1 || H != 256 || W != 256 || in_dtype != DGSCT_F32 || T < 2 || T > FE_MAX_T || !bn_scale || !bn_shift) {
-      set_error("%s: audio mode takes an fp32 log-mel of 2 .. %d frames, bn scale / shift, in_chans = 1 and a 256 x 256 image", who, FE_MAX_T);
-      return 2;
-    }
-    a.T = T; a.tscale = (float)(T - 1) / (float)(FE_MAX_T - 1);
-  } else if (mode == DGSCT_PATCH_IMAGE) {
-    if ((in_chans != 1 && in_chans != 3) || H < 4 || W < 4 || H % 4 || W % 4) {
-      set_error("%s: image mode takes in_chans 1 or 3 and H, W multiples of 4 (got %d, %d x %d)", who, in_chans, H, W); return 2;
-    }
-  } else { set_error("%s: unknown mode %d", who, mode); return 2; }
-  a.H = H; a.W = W; a.Hp = H / 4; a.Wp = W / 4;
-  a.tokens = (long)B * a.Hp * a.Wp;
-  if (a.tokens * C > 0x7fffffffffLL || (long)B * in_chans * H * W > 0x7fffffffffLL) { set_error("%s: tensor too large", who); return 2; }
+  if (!fe_patch_check(who, mode, in_dtype, out_dtype, B, in_chans, H, W, T, C, x, bn_scale, bn_shift, weight, bias, ln_weight, ln_bias, eps, a)) return 2;
+  a.out = out; a.odt = out_dtype;
   hipStream_t s = (hipStream_t)stream;
   clear_async();
   if (mode == DGSCT_PATCH_AUDIO) patch_embed_nj<1, true>(a, s);
   else if (in_chans == 1) patch_embed_nj<1, false>(a, s);
   else patch_embed_nj<3, false>(a, s);
+  check_async(who);
+  return has_error() ? 1 : 0;
+}
+
+int64_t dgsct_patch_embed_params_ws_floats(int mode, int B, int in_chans, int H, int W, int C) {
+  clear_error();
+  const char* who = "dgsct_patch_embed_params_ws_floats";
+  if (!fe_patch_geometry(who, mode, B, in_chans, H, W, mode == DGSCT_PATCH_AUDIO ? 2 : 0, C)) return -1;
+  const long tokens = (long)B * (H / 4) * (W / 4);
+  return pe_bwd_rows(tokens) * pe_bwd_row_floats(mode, in_chans, C);
+}
+
+int dgsct_patch_embed_backward_params(int mode, int in_dtype, int dout_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
+                                      const float* bn_scale, const float* bn_shift, const float* bn_pivot, const float* weight, const float* bias,
+                                      const float* ln_weight, const float* ln_bias, float eps, const void* dout, float* dweight, float* dbias,
+                                      float* dln_weight, float* dln_bias, float* dbn, float* ws, void* stream) {
+  clear_error();
+  const char* who = "dgsct_patch_embed_backward_params";
+  if (!dout || !dweight || !dbias || !dln_weight || !dln_bias || !ws) { set_error("%s: NULL argument", who); return 2; }
+  if (mode == DGSCT_PATCH_AUDIO && (!bn_pivot || !dbn)) { set_error("%s: audio mode needs bn_pivot and dbn", who); return 2; }
+  PatchBwdArgs a{};
+  if (!fe_patch_check(who, mode, in_dtype, dout_dtype, B, in_chans, H, W, T, C, x, bn_scale, bn_shift, weight, bias, ln_weight, ln_bias, eps, a.f)) return 2;
+  a.dout = dout; a.ddt = dout_dtype; a.pivot = bn_pivot; a.ws = ws; a.rs = (int)pe_bwd_row_floats(mode, in_chans, C);
+  hipStream_t s = (hipStream_t)stream;
+  clear_async();
+  if (mode == DGSCT_PATCH_AUDIO) patch_embed_bwd_nj<1, true>(a, dweight, dbias, dln_weight, dln_bias, dbn, s);
+  else if (in_chans == 1) patch_embed_bwd_nj<1, false>(a, dweight, dbias, dln_weight, dln_bias, nullptr, s);
+  else patch_embed_bwd_nj<3, false>(a, dweight, dbias, dln_weight, dln_bias, nullptr, s);
   check_async(who);
   return has_error() ? 1 : 0;
 }

@@ -1,7 +1,7 @@
 """What feeds the layer loop (the part in front of the first block): the reference's audio front end
 ``spectrogram_extractor -> logmel_extractor -> bn0 -> reshape_wav2img -> patch_embed`` (DG-SCT/AVE/nets/net_trans.py:857-876;
-htsat.py:443-459, 719-734; layers.py:56-86) and the visual ``swin.patch_embed`` (net_trans.py:855), as two frozen, forward-only modules
-with the reference's ``state_dict`` names:
+htsat.py:443-459, 719-734; layers.py:56-86) and the visual ``swin.patch_embed`` (net_trans.py:855), as two modules with the reference's
+``state_dict`` names, frozen and forward-only unless built with ``trainable=True``:
 
     HTSATFrontEnd   waveform [B, L] -> tokens [B, 4096, embed_dim]      two or three launches of csrc/frontend.hip (ops.logmel, its
                     statistics reduction in train mode, ops.patch_embed in audio mode); no tensor larger than the log-mel exists
@@ -10,6 +10,15 @@ with the reference's ``state_dict`` names:
 Both dispatch like the backbone blocks: ``fused=None`` runs the HIP path on GPU tensors; ``fused=False`` (or CPU tensors) runs an ATen
 formulation of the same maths (torch.stft, matmul, F.batch_norm, F.interpolate, F.conv2d, F.layer_norm) -- the CPU-testable restatement
 and the A/B partner on the GPU.
+
+``trainable=True`` (AVS-S4 trains everything outside ``'ViT'`` / ``'swin'``, avs_s4/train.py:145-163, so ``htsat.bn0.*`` and
+``htsat.patch_embed.*`` train, ``bn0`` on batch statistics) leaves ``proj.*``, ``norm.*``, ``bn0.weight`` and ``bn0.bias`` requiring grad --
+never ``melW``, the waveform or the image -- and runs the forward under autograd.  On the kernel path the forward is the same launches and the
+backward is ONE call, ``dgsct_patch_embed_backward_params`` (``ops.patch_embed_train``), which recomputes the convolution and the
+LayerNorm statistics from the log-mel / the image: nothing token-sized is kept for it.  ``fused=True`` takes the kernels (and raises when the
+library lacks the export), ``fused=False`` / CPU is the ATen formulation under plain autograd, and ``fused=None`` follows
+``_KERNELS_FASTER_TRAIN`` (the kinds measured faster, profiles/frontend_train_bench.txt).  With grad disabled, or with every one of those parameters frozen again, a
+trainable module runs exactly the frozen path.
 
 **Parity against torchlibrosa / librosa is unpinned**: neither is installed here, and the oracle cannot import the front end of
 ``htsat.py``.  The pin is to the published formulas evaluated in float64 (tests/test_frontend_cpu.py, tests/test_frontend_gpu.py): the
@@ -74,15 +83,37 @@ def _use_fused(fused: Optional[bool], x: torch.Tensor, who: str) -> bool:
 
 def _refuse_grad(who: str, x: torch.Tensor):
     if x.requires_grad:
-        raise RuntimeError(f"dg-sct_amd: {who} is forward-only: its input requires grad (detach it; the front end is frozen)")
+        raise RuntimeError(f"dg-sct_amd: {who} is forward-only: its input requires grad (detach it; no input gradient is built, trainable or not)")
+
+
+# `fused=None` with trainable=True takes the kernels only for the kinds listed here: those where `tools/frontend_bench.py --train` measured
+# the kernels' slowest forward + backward window faster than the fastest window of the ATen formulation on the same GPU
+# (profiles/frontend_train_bench.txt).  A kind that is not listed stays ATen under fused=None, and fused=True is the opt-in.
+_KERNELS_FASTER_TRAIN: frozenset = frozenset({"audio", "image"})
+
+
+def _train_through_kernels(fused: Optional[bool], x: torch.Tensor, lib, who: str, kind: str) -> bool:
+    """which formulation a forward that wants parameter gradients takes; kind: "audio" (HTSATFrontEnd) | "image" (PatchEmbed)"""
+    if fused is None and not (x.is_cuda and kind in _KERNELS_FASTER_TRAIN):
+        return False
+    if not _use_fused(fused, x, who):
+        return False
+    lib = lib or ops._lib.default_lib()
+    if not lib.has_patch_embed_params():
+        if fused:
+            raise RuntimeError(f"dg-sct_amd: {who}(trainable=True, fused=True): {lib.path} does not export dgsct_patch_embed_backward_params "
+                               f"(fused=None / False for the ATen formulation)")
+        return False
+    return True
 
 
 class PatchEmbed(nn.Module):
     """``PatchEmbed`` of timm 0.6.12 / layers.py:56-86 at patch 4, stride 4: ``norm(proj(x).flatten(2).transpose(1, 2))``; keys
-    ``proj.{weight,bias}``, ``norm.{weight,bias}``.  Frozen, forward-only.  out_dtype None: the image's dtype."""
+    ``proj.{weight,bias}``, ``norm.{weight,bias}``.  Frozen and forward-only; trainable=True: the four parameters require grad and the forward
+    runs under autograd (no input gradient either way).  out_dtype None: the image's dtype."""
 
     def __init__(self, img_size, patch_size: int = 4, in_chans: int = 3, embed_dim: int = 128, fused: Optional[bool] = None, lib=None,
-                 out_dtype: Optional[torch.dtype] = None):
+                 out_dtype: Optional[torch.dtype] = None, trainable: bool = False):
         super().__init__()
         if patch_size != 4:
             raise ValueError("dg-sct_amd: PatchEmbed is built for 4 x 4 patches at stride 4 (every reference backbone)")
@@ -97,21 +128,38 @@ class PatchEmbed(nn.Module):
         self.fused, self.lib, self.out_dtype = fused, lib, out_dtype
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=4, stride=4)
         self.norm = nn.LayerNorm(embed_dim)
-        self.requires_grad_(False)
+        self.trainable = bool(trainable)
+        self.requires_grad_(self.trainable)
+
+    def _wants_grad(self) -> bool:
+        return self.trainable and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def _tokens_aten(self, img: torch.Tensor) -> torch.Tensor:
         x = F.conv2d(img.float(), self.proj.weight, self.proj.bias, stride=4)
         return F.layer_norm(x.flatten(2).transpose(1, 2), (self.embed_dim,), self.norm.weight, self.norm.bias, self.norm.eps)
 
-    @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 4 or x.shape[1] != self.in_chans or tuple(x.shape[2:]) != self.img_size:
             raise RuntimeError(f"dg-sct_amd: PatchEmbed: input {tuple(x.shape)} does not match [B, {self.in_chans}, {self.img_size[0]}, {self.img_size[1]}]")
         _refuse_grad("PatchEmbed", x)
         out_dtype = self.out_dtype or x.dtype
+        if self._wants_grad():
+            if _train_through_kernels(self.fused, x, self.lib, "PatchEmbed", "image"):
+                return ops.patch_embed_train(x.contiguous(), self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps,
+                                             out_dtype=out_dtype, lib=self.lib)
+            return self._tokens_aten(x).to(out_dtype)
+        with torch.no_grad():
+            return self._forward_frozen(x, out_dtype)
+
+    def _frozen_params(self):
+        """proj.weight, proj.bias, norm.weight, norm.bias as `ops.patch_embed` takes them (it refuses tensors that require grad: a trainable
+        module evaluated without a graph hands it detached views)"""
+        ps = (self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias)
+        return tuple(t.detach() for t in ps) if self.trainable else ps
+
+    def _forward_frozen(self, x: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
         if _use_fused(self.fused, x, "PatchEmbed"):
-            return ops.patch_embed(x.contiguous(), self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps,
-                                   out_dtype=out_dtype, lib=self.lib)
+            return ops.patch_embed(x.contiguous(), *self._frozen_params(), self.norm.eps, out_dtype=out_dtype, lib=self.lib)
         return self._tokens_aten(x).to(out_dtype)
 
 
@@ -129,12 +177,14 @@ class HTSATFrontEnd(nn.Module):
     ``spectrogram_extractor.stft.conv_{real,imag}.weight`` are checked against the Hann-windowed DFT basis and dropped (they are functions
     of the constants; a basis more than 1e-5 away -- entries are <= 1, so fp32 rounding plus margin -- raises; ``conv_imag`` is accepted
     with either sign, +sin or -sin, because only the power is used).  ``bn0`` follows the module's mode: running statistics in eval mode, batch statistics
-    over (B, T) per mel bin plus the running-statistics update in train mode.  Frozen, forward-only.  out_dtype None: fp32."""
+    over (B, T) per mel bin plus the running-statistics update in train mode.  Frozen and forward-only; trainable=True: ``bn0.weight``,
+    ``bn0.bias`` and the four ``patch_embed`` parameters require grad (``melW`` never does) and the forward runs under autograd; the statistics
+    of ``bn0`` are functions of the waveform and carry no gradient.  out_dtype None: fp32."""
 
     _DERIVED = ("spectrogram_extractor.stft.conv_real.weight", "spectrogram_extractor.stft.conv_imag.weight")
 
     def __init__(self, embed_dim: int = 96, spec_size: int = 256, sample_rate: int = 32000, fmin: float = 50, fmax: float = 14000,
-                 fused: Optional[bool] = None, lib=None, out_dtype: Optional[torch.dtype] = None):
+                 fused: Optional[bool] = None, lib=None, out_dtype: Optional[torch.dtype] = None, trainable: bool = False):
         super().__init__()
         if spec_size != 256:
             raise ValueError("dg-sct_amd: HTSATFrontEnd is built for spec_size 256 (64 mel bins x 4 time quarters, every reference config)")
@@ -142,8 +192,12 @@ class HTSATFrontEnd(nn.Module):
         self.fused, self.lib, self.out_dtype = fused, lib, out_dtype
         self.logmel_extractor = _MelBank(slaney_mel_filterbank(sample_rate, N_FFT, N_MELS, fmin, fmax))
         self.bn0 = nn.BatchNorm2d(N_MELS)
-        self.patch_embed = PatchEmbed(spec_size, 4, 1, embed_dim, fused=fused, lib=lib, out_dtype=out_dtype)
+        self.patch_embed = PatchEmbed(spec_size, 4, 1, embed_dim, fused=fused, lib=lib, out_dtype=out_dtype, trainable=trainable)
+        self.trainable = bool(trainable)
         self.requires_grad_(False)
+        if self.trainable:
+            self.bn0.requires_grad_(True)
+            self.patch_embed.requires_grad_(True)
         self._ranges = None            # (melW version, device, ops.mel_ranges(melW))
 
     # -- checkpoint loading ------------------------------------------------------------------------------------------------------------
@@ -179,8 +233,9 @@ class HTSATFrontEnd(nn.Module):
         power = (z.real * z.real + z.imag * z.imag).transpose(1, 2)            # [B, T, 513]
         return 10.0 * torch.log10(torch.clamp(power @ self.logmel_extractor.melW.to(waveform.dtype), min=1e-10))
 
-    def _bn_affine(self, mean: Optional[torch.Tensor], var: Optional[torch.Tensor], n: int):
-        """scale / shift [64] of bn0 from the batch statistics (train mode: also the running-statistics update) or the running ones"""
+    def _bn_statistics(self, mean: Optional[torch.Tensor], var: Optional[torch.Tensor], n: int):
+        """the (mean, biased variance) bn0 normalises with: the batch statistics (train mode: also the running-statistics update) or the
+        running ones"""
         bn = self.bn0
         if mean is not None:
             if bn.track_running_stats and bn.running_mean is not None:
@@ -190,6 +245,12 @@ class HTSATFrontEnd(nn.Module):
                 bn.running_var.mul_(1.0 - mom).add_(var * (n / max(n - 1, 1)), alpha=mom)
         else:
             mean, var = bn.running_mean, bn.running_var
+        return mean, var
+
+    def _bn_affine(self, mean: Optional[torch.Tensor], var: Optional[torch.Tensor], n: int):
+        """scale / shift [64] of bn0 from `_bn_statistics`"""
+        bn = self.bn0
+        mean, var = self._bn_statistics(mean, var, n)
         scale = bn.weight * torch.rsqrt(var + bn.eps)
         return scale.contiguous(), (bn.bias - mean * scale).contiguous()
 
@@ -207,7 +268,14 @@ class HTSATFrontEnd(nn.Module):
         x = x.permute(0, 1, 3, 2, 4).reshape(B, 1, self.spec_size, self.spec_size)     # image[q*64 + f][t'] = x[q*256 + t'][f]
         return self.patch_embed._tokens_aten(x)
 
-    @torch.no_grad()
+    def _wants_grad(self) -> bool:
+        if not (self.trainable and torch.is_grad_enabled()):
+            return False
+        if self.logmel_extractor.melW.requires_grad:
+            raise RuntimeError("dg-sct_amd: HTSATFrontEnd: logmel_extractor.melW requires grad, and no gradient into the mel matrix is built "
+                               "(freeze it: a name rule that unfreezes everything under 'htsat' unfreezes it too)")
+        return any(p.requires_grad for p in self.parameters())
+
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
         if waveform.dim() != 2 or waveform.dtype != torch.float32:
             raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd takes an fp32 waveform [B, L] (got {tuple(waveform.shape)} {waveform.dtype})")
@@ -220,6 +288,29 @@ class HTSATFrontEnd(nn.Module):
             raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd: {L} samples give {T} frames, more than the {MAX_FRAMES} the {self.spec_size} x "
                                f"{self.spec_size} image holds (the reference's random crop_wav branch is not built)")
         out_dtype = self.out_dtype or torch.float32
+        if self._wants_grad():
+            return self._forward_trainable(waveform, B, T, out_dtype)
+        with torch.no_grad():
+            return self._forward_frozen(waveform, B, T, out_dtype)
+
+    def _forward_trainable(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype) -> torch.Tensor:
+        """the waveform and melW are data: the log-mel (and the statistics of bn0) are made without a graph, autograd starts at bn0"""
+        melW, pe, bn = self.logmel_extractor.melW, self.patch_embed, self.bn0
+        if not _train_through_kernels(self.fused, waveform, self.lib, "HTSATFrontEnd", "audio"):
+            with torch.no_grad():
+                lm = self.logmel_aten(waveform)
+            return self._tokens_aten(lm).to(out_dtype)
+        with torch.no_grad():
+            if self.training:
+                lm, mean, var = ops.logmel(waveform.contiguous(), melW, want_stats=True, lib=self.lib, ranges=self._mel_ranges())
+                mean, var = self._bn_statistics(mean, var, B * T)
+            else:
+                lm = ops.logmel(waveform.contiguous(), melW, lib=self.lib, ranges=self._mel_ranges())
+                mean, var = self._bn_statistics(None, None, B * T)
+        return ops.patch_embed_train(lm, pe.proj.weight, pe.proj.bias, pe.norm.weight, pe.norm.bias, pe.norm.eps, out_dtype=out_dtype,
+                                     bn_weight=bn.weight, bn_bias=bn.bias, mean=mean, var=var, bn_eps=bn.eps, lib=self.lib)
+
+    def _forward_frozen(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype) -> torch.Tensor:
         if not _use_fused(self.fused, waveform, "HTSATFrontEnd"):
             return self._tokens_aten(self.logmel_aten(waveform)).to(out_dtype)
         melW, pe = self.logmel_extractor.melW, self.patch_embed
@@ -229,5 +320,4 @@ class HTSATFrontEnd(nn.Module):
         else:
             lm = ops.logmel(waveform.contiguous(), melW, lib=self.lib, ranges=self._mel_ranges())
             scale, shift = self._bn_affine(None, None, B * T)
-        return ops.patch_embed(lm, pe.proj.weight, pe.proj.bias, pe.norm.weight, pe.norm.bias, pe.norm.eps, out_dtype=out_dtype,
-                               bn_scale=scale, bn_shift=shift, lib=self.lib)
+        return ops.patch_embed(lm, *pe._frozen_params(), pe.norm.eps, out_dtype=out_dtype, bn_scale=scale, bn_shift=shift, lib=self.lib)

@@ -832,7 +832,8 @@ N_FFT, HOP, N_MELS, MAX_FRAMES = 1024, 320, 64, 1024
 
 
 def _no_grad_inputs(who: str, *tensors):
-    """the front end is forward-only (inputs are data, parameters frozen): refuse to cut a graph silently"""
+    """these calls are forward-only (inputs are data, parameters frozen; `patch_embed_train` is the one with parameter gradients):
+    refuse to cut a graph silently"""
     for t in tensors:
         if t is not None and t.requires_grad:
             raise RuntimeError(f"dg-sct_amd: {who} is forward-only: an input requires grad (detach it; the front end's parameters are frozen)")
@@ -947,6 +948,84 @@ def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_we
                                 weight.data_ptr(), bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps), out.data_ptr(),
                                 _stream_of(x))
     return out
+
+
+class _PatchEmbedTrainFn(torch.autograd.Function):
+    """forward: `patch_embed` (the same launch as the frozen path); backward: dgsct_patch_embed_backward_params, which recomputes the
+    convolution and the LayerNorm statistics from x -- nothing token-sized is saved"""
+
+    @staticmethod
+    def forward(ctx, lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, eps, bn_eps, out_dtype):
+        audio = bn_weight is not None
+        scale = shift = rstd = None
+        if audio:
+            rstd = torch.rsqrt(var + bn_eps)
+            scale = bn_weight.detach() * rstd                          # (the arithmetic of HTSATFrontEnd._bn_affine: the tokens equal the frozen path's)
+            shift = (bn_bias.detach() - mean * scale).contiguous()
+            scale = scale.contiguous()
+        w, b, lw, lb = weight.detach(), bias.detach(), ln_weight.detach(), ln_bias.detach()
+        out = patch_embed(x, w, b, lw, lb, eps, out_dtype, scale, shift, lib=lib)
+        ctx.lib, ctx.eps, ctx.audio = lib, float(eps), audio
+        ctx.save_for_backward(x, w, b, lw, lb, *((scale, shift, mean.contiguous(), rstd) if audio else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, b, lw, lb = ctx.saved_tensors[:5]
+        scale, shift, mean, rstd = ctx.saved_tensors[5:] if ctx.audio else (None,) * 4
+        C_ = w.shape[0]
+        if ctx.audio:
+            B, T, in_chans, H, W = x.shape[0], x.shape[1], 1, 256, 256
+        else:
+            (B, in_chans, H, W), T = x.shape, 0
+        if dout.dtype not in (torch.float32, torch.bfloat16):
+            dout = dout.float()
+        dout = dout.contiguous()
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dw, db, dlw, dlb = torch.empty_like(w), torch.empty(C_, **f32), torch.empty(C_, **f32), torch.empty(C_, **f32)     # (written by the call)
+        dbn = torch.empty(2, N_MELS, **f32) if ctx.audio else None
+        mode = _lib.PATCH_AUDIO if ctx.audio else _lib.PATCH_IMAGE
+        ws = torch.empty(ctx.lib.patch_embed_params_ws_floats(mode, B, in_chans, H, W, C_), **f32)
+        code = lambda dt: _lib.F32 if dt == torch.float32 else _lib.BF16
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _mark_stream_use(x, w, b, lw, lb, scale, shift, mean, dout)
+        with _dev_guard(x):
+            ctx.lib.patch_embed_backward_params(mode, code(x.dtype), code(dout.dtype), B, in_chans, H, W, T, C_, x.data_ptr(), ptr(scale), ptr(shift),
+                                                ptr(mean), w.data_ptr(), b.data_ptr(), lw.data_ptr(), lb.data_ptr(), ctx.eps, dout.data_ptr(),
+                                                dw.data_ptr(), db.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), ptr(dbn), ws.data_ptr(), _stream_of(x))
+        need = ctx.needs_input_grad
+        # the pivot of the kernel's sums is the mean bn0 normalised with: d bn0.weight = rstd g1, d bn0.bias = g0
+        dbw = dbn[0] * rstd if ctx.audio and need[6] else None
+        dbb = dbn[1] if ctx.audio and need[7] else None
+        return (None, None, dw if need[2] else None, db if need[3] else None, dlw if need[4] else None, dlb if need[5] else None, dbw, dbb,
+                None, None, None, None, None)
+
+
+def patch_embed_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor,
+                      eps: float = 1e-5, out_dtype: Optional[torch.dtype] = None, bn_weight: Optional[torch.Tensor] = None,
+                      bn_bias: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, var: Optional[torch.Tensor] = None,
+                      bn_eps: float = 1e-5, lib: Optional[Lib] = None) -> torch.Tensor:
+    """`patch_embed` for a TRAINABLE front end: the same launch forward, and weight / bias / ln_weight / ln_bias (fp32) receive fp32
+    gradients from dgsct_patch_embed_backward_params (dOut fp32 or bf16, every sum in fp32, no atomics: a repeated backward is bit-identical).
+    Audio mode (bn_weight, bn_bias, mean, var [64] given; x the log-mel [B, T, 64]): `bn0` enters as its own tensors, scale = bn_weight
+    rsqrt(var + bn_eps) and shift = bn_bias - mean scale are formed here, and bn_weight / bn_bias receive their gradients directly (mean and
+    var -- running or batch statistics -- are functions of data and get none).  x may not require grad: no input gradient exists."""
+    who = "patch_embed_train"
+    audio = any(t is not None for t in (bn_weight, bn_bias, mean, var))
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("dg-sct_amd: patch_embed_train needs CUDA/HIP tensors (no CPU fallback; fused=False is the ATen formulation)")
+    if audio:
+        for n, t in (("bn_weight", bn_weight), ("bn_bias", bn_bias), ("mean", mean), ("var", var)):
+            if t is None:
+                raise RuntimeError("dg-sct_amd: patch_embed_train (audio): bn_weight, bn_bias, mean and var go together")
+            _dev_f32(who, n, t, (N_MELS,), x.device)
+    if x.requires_grad or (audio and (mean.requires_grad or var.requires_grad)):
+        raise RuntimeError(f"dg-sct_amd: {who} returns parameter gradients only: x (and bn0's mean / var) may not require grad (detach them)")
+    lib = lib or _lib.default_lib()
+    if not lib.has_patch_embed_params():
+        raise RuntimeError(f"dg-sct_amd: {who}: {lib.path} does not export dgsct_patch_embed_backward_params (a library without the front "
+                           f"end's parameter gradients; fused=False, the ATen formulation, trains without it)")
+    return _PatchEmbedTrainFn.apply(lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, float(eps), float(bn_eps), out_dtype)
 
 
 # ---- patch merging between two backbone stages (SURVEY.md 8(f) row f4; csrc/pmerge.hip) ------------------------------------------------

@@ -258,7 +258,7 @@ int dgsct_layer_norm_backward(int dtype, int64_t rows, int C, const void* dout, 
                               const float* rstd, float eps, void* dx, float* dw, float* db, float* scratch, void* stream);
 
 /* ---- audio / image front ends: waveform -> log-mel -> patch tokens (csrc/frontend.hip) ----------------------
- * Forward only (inputs are data, the sub-modules are frozen).  Optional exports: a library built without csrc/frontend.hip (the host
+ * The inputs are data: no call returns an input gradient.  Optional exports: a library built without csrc/frontend.hip (the host
  * emulation of the CPU tests) leaves them undefined, so bind them by name.
  *
  * dgsct_logmel_forward replaces `spectrogram_extractor` + `logmel_extractor` (DG-SCT/AVE/nets/net_trans.py:857-858, htsat.py:443-449):
@@ -278,7 +278,19 @@ int dgsct_layer_norm_backward(int dtype, int64_t rows, int C, const void* dout, 
  *     bn_scale / bn_shift [64] (x * scale[f] + shift[f]), and `reshape_wav2img` (htsat.py:719-734) is address arithmetic of the loads:
  *     bicubic interpolation along time T -> 1024 (align_corners, A = -0.75, taps clamped; a plain copy when T == 1024), then
  *     image[q*64 + f][t'] = logmel'[q*256 + t'][f].  Neither the interpolated tensor nor the image exists in memory.
- * Asynchronous on `stream`; 0 or an error code (dgsct_logmel_scratch_floats: -1). */
+ *
+ * dgsct_patch_embed_backward_params (a TRAINABLE front end; still DGSCT_VERSION 101, bind it by name): the gradients of the six tensors
+ * that train in front of the first HTS-AT block, from dout [B][(H/4) (W/4)][C] (dout_dtype DGSCT_F32 | DGSCT_BF16), all in fp32:
+ *   dweight [C][in_chans][4][4], dbias / dln_weight / dln_bias [C]; DGSCT_PATCH_AUDIO also dbn [2][64] = per mel bin f
+ *     g1[f] = sum dpix (S(lm) - bn_pivot[f])  and  g0[f] = sum dpix     (dpix = the gradient at the `bn0` output, S = the bicubic stretch),
+ *     so that d bn0.bias = g0 and d bn0.weight = rstd (g1 + (bn_pivot - mean) g0); pass the mean `bn0` normalised with as bn_pivot [64]
+ *     (then d bn0.weight = rstd g1, and nothing cancels in fp32).  Mean and variance are functions of data and carry no gradient, in
+ *     batch-statistics mode too.  DGSCT_PATCH_IMAGE: bn_* unused, dbn may be NULL.
+ *   The same x, bn_scale, bn_shift, weights, eps, limits and argument checks as the forward, whose convolution and LayerNorm statistics are
+ *   recomputed from x: the forward stores nothing for this call.  No gradient for x.
+ *   ws: dgsct_patch_embed_params_ws_floats(...) floats (one partial row per workgroup; a second launch sums the rows in a fixed order).
+ *   Every output is written by the call (nothing needs zeroing), without atomics: two calls on the same inputs agree bit for bit.
+ * Asynchronous on `stream`; 0 or an error code (dgsct_logmel_scratch_floats / dgsct_patch_embed_params_ws_floats: -1). */
 #define DGSCT_PATCH_IMAGE 0
 #define DGSCT_PATCH_AUDIO 1
 int64_t dgsct_logmel_scratch_floats(int B, int64_t L, int n_fft, int hop, int n_mels);
@@ -287,6 +299,13 @@ int dgsct_logmel_forward(int B, int64_t L, int n_fft, int hop, int n_mels, const
 int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
                               const float* bn_scale, const float* bn_shift, const float* weight, const float* bias, const float* ln_weight,
                               const float* ln_bias, float eps, void* out, void* stream);
+int64_t dgsct_patch_embed_params_ws_floats(int mode, int B, int in_chans, int H, int W, int C);
+int dgsct_patch_embed_backward_params(int mode, int in_dtype, int dout_dtype, int B, int in_chans, int H, int W, int T, int C, const void* x,
+                                      const float* bn_scale, const float* bn_shift, const float* bn_pivot /* [64], audio only */,
+                                      const float* weight, const float* bias, const float* ln_weight, const float* ln_bias, float eps,
+                                      const void* dout, float* dweight /* [C][IC][4][4] */, float* dbias, float* dln_weight,
+                                      float* dln_bias /* [C] */, float* dbn /* [2][64]: g1, g0; audio only, else NULL */, float* ws,
+                                      void* stream);
 
 /* ---- patch merging between two backbone stages (csrc/pmerge.hip) -----------------------------------------------------------------
  * The 2 x 2 merge of `f_v = my_blk.downsample(f_v)` / `f_a = htsat_blk.downsample(f_a)` (DG-SCT/AVE/nets/net_trans.py:914-916).  Optional

@@ -2,7 +2,12 @@
 160 images of 3 x 192 x 192 -> Swin-V2 tokens, each against the module's own fused=False ATen formulation on the same GPU.
 Method: 3 warm-up calls, then `--reps` windows of `--inner` calls between two device events; the median window is reported (min / max
 beside it).  Traffic floor of the audio path: waveform in, log-mel out and back in, tokens out.
-usage: python tools/frontend_bench.py [--batch 160] [--samples 320000] [--reps 7] [--inner 5] [--embed-dim 96]"""
+`--train` times the TRAINABLE modules instead (forward + backward with the six / four parameter gradients, fp32 masters, train mode): the
+kernels (trainable=True, fused=True: the forward's launches + dgsct_patch_embed_backward_params) against the same module with fused=False,
+same GPU, same run, same method, and says what frontend._KERNELS_FASTER_TRAIN should hold.  Traffic floor of the backward: log-mel (or
+image) read + dOut read.
+usage: python tools/frontend_bench.py [--batch 160] [--samples 320000] [--reps 7] [--inner 5] [--embed-dim 96] [--train]
+       (profiles/frontend_bench.txt and profiles/frontend_train_bench.txt are its output)"""
 import argparse
 import os
 import statistics
@@ -21,6 +26,7 @@ ap.add_argument("--samples", type=int, default=320000)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--inner", type=int, default=5)
 ap.add_argument("--embed-dim", type=int, default=96)
+ap.add_argument("--train", action="store_true")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("frontend_bench: needs a GPU (a timing taken elsewhere says nothing)")
@@ -55,6 +61,61 @@ B, L, C = args.batch, args.samples, args.embed_dim
 T = L // 320 + 1
 gen = torch.Generator().manual_seed(0)
 wave = (0.1 * torch.randn(B, L, generator=gen)).to(dev)
+
+
+def train_rows(tag, mods, x, cot, floor_bytes):
+    """fwd / bwd / fwd+bwd of mods = {"fused": ..., "ATen": ...}; returns whether the kernels' slowest fwd+bwd window beat ATen's fastest"""
+    res = {}
+    for name, m in mods.items():
+        params = [q for q in m.parameters() if q.requires_grad]
+
+        def step():
+            for q in params:
+                q.grad = None
+            m(x).backward(cot)
+
+        out = m(x)
+        res[name] = (timed(lambda: m(x)), timed(lambda: torch.autograd.grad(out, params, cot, retain_graph=True)), timed(step))
+        del out
+    for i, what in enumerate(("fwd", "bwd", "fwd+bwd")):
+        f, a = res["fused"][i], res["ATen"][i]
+        print(f"{tag:<44} {what:<8} {f[0]:9.1f} ({f[1]:.1f}, {f[2]:.1f})   {a[0]:9.1f} ({a[1]:.1f}, {a[2]:.1f})   {a[0] / f[0]:6.2f}x", flush=True)
+    bwd = res["fused"][1][0]
+    print(f"{tag:<44} backward traffic floor {floor_bytes / 1e6:.1f} MB at 8 TB/s = {floor_bytes / 8e6:.1f} us -> achieved fraction "
+          f"{floor_bytes / 8e6 / bwd:.3f}\n", flush=True)
+    return res["fused"][2][2] < res["ATen"][2][1]
+
+
+if args.train:
+    from dgsct_amd import frontend
+    print(f"trainable front end (fp32 master parameters, train mode), batch {B}; {torch.cuda.get_device_name(0)}; times in us: median (min, max) "
+          f"of {args.reps} windows of {args.inner} calls")
+    print("fused = trainable=True, fused=True: the forward's launches + dgsct_patch_embed_backward_params;  ATen = the same module with fused=False")
+    print(f"{'module':<44} {'what':<8} {'fused':>28}   {'ATen':>28}   ATen/fused")
+    faster = {"audio": [], "image": []}
+    for out_dtype in (torch.bfloat16, torch.float32):
+        es = 2 if out_dtype == torch.bfloat16 else 4
+        mods = {"fused": HTSATFrontEnd(embed_dim=C, out_dtype=out_dtype, trainable=True, fused=True).to(dev).train(),
+                "ATen": HTSATFrontEnd(embed_dim=C, out_dtype=out_dtype, trainable=True, fused=False).to(dev).train()}
+        cot = torch.randn(B, 4096, C, generator=gen).to(dev, out_dtype)
+        faster["audio"].append(train_rows(f"HTSATFrontEnd [{B}, {L}] -> {'bf16' if es == 2 else 'fp32'} x {C}", mods, wave, cot, B * T * 64 * 4 + B * 4096 * C * es))
+        del mods, cot
+        torch.cuda.empty_cache()
+    del wave
+    torch.cuda.empty_cache()
+    for Cv in (128, 192):
+        img = torch.randn(B, 3, 192, 192, generator=gen).to(dev, torch.bfloat16)
+        mods = {"fused": PatchEmbed(192, in_chans=3, embed_dim=Cv, out_dtype=torch.bfloat16, trainable=True, fused=True).to(dev),
+                "ATen": PatchEmbed(192, in_chans=3, embed_dim=Cv, out_dtype=torch.bfloat16, trainable=True, fused=False).to(dev)}
+        cot = torch.randn(B, 2304, Cv, generator=gen).to(dev, torch.bfloat16)
+        faster["image"].append(train_rows(f"PatchEmbed [{B}, 3, 192, 192] bf16 -> bf16 x {Cv}", mods, img, cot, img.numel() * 2 + B * 2304 * Cv * 2))
+        del mods, cot, img
+        torch.cuda.empty_cache()
+    print(f"forward + backward: kinds where the kernels' slowest window was faster than ATen's fastest in every row (what "
+          f"frontend._KERNELS_FASTER_TRAIN should hold): {sorted(k for k, v in faster.items() if all(v))}; it holds "
+          f"{sorted(frontend._KERNELS_FASTER_TRAIN)}")
+    sys.exit(0)
+
 print(f"audio: waveform [{B}, {L}] fp32 -> {T} frames -> tokens [{B}, 4096, {C}]; {torch.cuda.get_device_name(0)}")
 for out_dtype in (torch.bfloat16, torch.float32):
     for training in (False, True):
