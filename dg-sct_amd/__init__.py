@@ -12,3 +12,5 @@ from .temporal import TemporalAttention, TemporalAttentionAVS, TemporalAttention
 from .backbone import FrozenBlocks, HTSATBlock, SwinV2Block         # noqa: F401
 from .frontend import HTSATFrontEnd, PatchEmbed                     # noqa: F401
 from .merging import AVETrunk, HTSATPatchMerging, SwinV2PatchMerging   # noqa: F401
+from .cmbs import CMBS                                              # noqa: F401
+from .model import AVENet                                           # noqa: F401

@@ -176,6 +176,17 @@ class Lib:
             self._pmerge_pws.restype = C.c_int64
         if self._pmerge_bwd_params is not None:
             self._pmerge_bwd_params.argtypes = [C.c_int] * 5 + [C.c_void_p] * 8 + [C.c_float] + [C.c_void_p] * 6
+        # optional (include/dgsct.h): the live part of the CMBS event head (csrc/head.hip); the host emulation lacks it
+        self._cmbs_ws = getattr(c, "dgsct_cmbs_head_ws_bytes", None)
+        self._cmbs_fwd = getattr(c, "dgsct_cmbs_head_forward", None)
+        self._cmbs_bwd = getattr(c, "dgsct_cmbs_head_backward", None)
+        if self._cmbs_ws is not None:
+            self._cmbs_ws.argtypes = [C.c_int] * 4
+            self._cmbs_ws.restype = C.c_int64
+        if self._cmbs_fwd is not None:
+            self._cmbs_fwd.argtypes = [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 16
+        if self._cmbs_bwd is not None:
+            self._cmbs_bwd.argtypes = [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 23
         if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
@@ -349,6 +360,33 @@ class Lib:
         (include/dgsct.h: dgsct_patch_merge_backward_params)"""
         self._check(self._pmerge(self._pmerge_bwd_params, "dgsct_patch_merge_backward_params")(
             mode, B, H, W, C_, dout, x, w_bf16, ln_w, ln_b, pre, mu, rstd, eps, dx, dw, dln_w, dln_b, ws, stream), "dgsct_patch_merge_backward_params")
+
+    def has_cmbs_head(self) -> bool:
+        """whether this library exports dgsct_cmbs_head_forward / _backward / _ws_bytes (csrc/head.hip)"""
+        return None not in (self._cmbs_ws, self._cmbs_fwd, self._cmbs_bwd)
+
+    def _cmbs(self, fn, name: str):
+        if fn is None:
+            raise RuntimeError(f"dg-sct_amd: {self.path} does not export {name} (a library without the CMBS event head)")
+        return fn
+
+    def cmbs_head_ws_bytes(self, T: int, B: int, D: int, K: int) -> int:
+        n = self._cmbs(self._cmbs_ws, "dgsct_cmbs_head_ws_bytes")(T, B, D, K)
+        if n < 0:
+            raise RuntimeError(f"dgsct_cmbs_head_ws_bytes failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def cmbs_head_forward(self, T, B, D, K, gamma, v, a, Wvc, bvc, Wac, bac, wc, bc, We, be, is_event, event, av, topmask, argmax, stream):
+        """pointers as ints (include/dgsct.h: dgsct_cmbs_head_forward)"""
+        self._check(self._cmbs(self._cmbs_fwd, "dgsct_cmbs_head_forward")(T, B, D, K, gamma, v, a, Wvc, bvc, Wac, bac, wc, bc, We, be, is_event,
+                                                                          event, av, topmask, argmax, stream), "dgsct_cmbs_head_forward")
+
+    def cmbs_head_backward(self, T, B, D, K, gamma, v, a, Wvc, Wac, wc, We, topmask, argmax, d_is, d_ev, d_av, dv, da, grads, ws, stream):
+        """grads: the eight gradient pointers (dWvc, dbvc, dWac, dbac, dwc, dbc, dWe, dbe) or None for a frozen head; cotangents, dv / da
+        and ws may be None (include/dgsct.h: dgsct_cmbs_head_backward)"""
+        grads = tuple(grads) if grads is not None else (None,) * 8
+        self._check(self._cmbs(self._cmbs_bwd, "dgsct_cmbs_head_backward")(T, B, D, K, gamma, v, a, Wvc, Wac, wc, We, topmask, argmax, d_is, d_ev,
+                                                                           d_av, dv, da, *grads, ws, stream), "dgsct_cmbs_head_backward")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

@@ -1,0 +1,69 @@
+"""``AVENet``: the AVE model from waveform + frames to the four tensors the training script consumes.
+
+Mirrors ``forward_swin`` (reference ``DG-SCT/AVE/nets/net_trans.py:848-934``) by chaining the pieces of this package:
+
+    patch_embed    PatchEmbed          ``self.swin.patch_embed(vis)``                                   (:855)
+    frontend       HTSATFrontEnd       spectrogram, log-mel, bn0, reshape_wav2img, htsat.patch_embed    (:857-876)
+    trunk          AVETrunk            the adapter / frozen-block loop, the merges, swin.norm, pooling   (:878-924)
+    temporal_attn  TemporalAttention   (:928-930)
+    CMBS           CMBS                (:932)
+
+The last two carry the reference's attribute names, so their ``state_dict`` keys are the reference's as they stand and
+``train.trainable_by_name`` finds them (``'temporal_attn'``, ``'CMBS'``, and ``'adapter_blocks'`` inside the trunk train; everything else
+is frozen).  The trunk's documented limit is inherited: one frozen block per adapter position, random initialisation; loading a reference
+checkpoint into the whole net is not provided.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from .cmbs import CMBS
+from .frontend import HTSATFrontEnd, PatchEmbed
+from .merging import AVETrunk
+from .stack import ave_stage_shapes
+from .temporal import TemporalAttention
+
+
+class AVENet(nn.Module):
+    """``forward(waveform [B*T, L] fp32, frames [B, T, 3, H, W]) -> (is_event_scores [T, B, 1], event_scores [B, 28],
+    audio_visual_gate [T, B, 1], av_score [B, 28])``, the return of ``forward_swin``.
+
+    ``stages``: the per-stage token counts and widths (default ``ave_stage_shapes("swinv2_base")``); ``T`` frames per clip (the reference
+    hard-codes 10); ``img_size``: the frames' side, ``(img_size / 4)^2`` must be the visual token count of stage 0; ``dtype``: the trunk's
+    compute dtype, the pooled features are cast to fp32 for the temporal module and the head as the reference runs them;
+    ``train_htsat=True`` keeps the audio front end and the audio side of the trunk trainable (AVS-S4's rule); ``head_fused`` is ``CMBS``'s
+    ``fused``; every other keyword goes to ``AVETrunk`` (``fused=``, ``opt=``, ``lib=``, ...)."""
+
+    def __init__(self, stages: Optional[Sequence[Dict[str, int]]] = None, T: int = 10, img_size: int = 192,
+                 dtype: torch.dtype = torch.bfloat16, train_htsat: bool = False, head_fused: Optional[bool] = None, **trunk_kw):
+        super().__init__()
+        stages = [dict(s) for s in (stages if stages is not None else ave_stage_shapes("swinv2_base"))]
+        if (img_size // 4) ** 2 != stages[0]["Nv"] or img_size % 4:
+            raise ValueError(f"dg-sct_amd: AVENet: {img_size} x {img_size} frames give {(img_size // 4) ** 2} patches, stage 0 expects {stages[0]['Nv']}")
+        if stages[0]["Na"] != 4096:
+            raise ValueError(f"dg-sct_amd: AVENet: the HTS-AT front end makes 4096 audio tokens, stage 0 expects {stages[0]['Na']}")
+        self.T, self.dtype = int(T), dtype
+        lib = trunk_kw.get("lib")
+        self.patch_embed = PatchEmbed(img_size, in_chans=3, embed_dim=stages[0]["Cv"], out_dtype=dtype, lib=lib)
+        self.frontend = HTSATFrontEnd(embed_dim=stages[0]["Ca"], out_dtype=dtype, lib=lib, trainable=bool(train_htsat))
+        self.trunk = AVETrunk(stages, dtype=dtype, train_htsat=train_htsat, **trunk_kw)
+        self.temporal_attn = TemporalAttention(video_dim=stages[-1]["Cv"], audio_dim=stages[-1]["Ca"], lib=lib)
+        self.CMBS = CMBS(None, fused=head_fused, lib=lib)
+
+    def forward(self, waveform: torch.Tensor, frames: torch.Tensor):
+        if frames.dim() != 5 or frames.shape[1] != self.T:
+            raise RuntimeError(f"dg-sct_amd: AVENet takes frames [B, {self.T}, 3, H, W] (got {tuple(frames.shape)})")
+        bs = frames.shape[0]
+        if waveform.dim() != 2 or waveform.shape[0] != bs * self.T:
+            raise RuntimeError(f"dg-sct_amd: AVENet takes one waveform per frame, [{bs * self.T}, L] (got {tuple(waveform.shape)})")
+        f_v = self.patch_embed(frames.reshape(bs * self.T, *frames.shape[2:]))          # 'b t c w h -> (b t) c w h'
+        f_a = self.frontend(waveform)
+        f_v, f_a, _, _ = self.trunk(f_v, f_a)                                           # [BT, 1, C] each
+        f_v = f_v.float().view(bs, self.T, -1)
+        f_a = f_a.float().view(bs, self.T, -1)
+        video_feature, audio_feature, audio_visual_gate = self.temporal_attn(f_v, f_a)
+        is_event_scores, event_scores, av_score = self.CMBS(video_feature, audio_feature)
+        return is_event_scores, event_scores, audio_visual_gate, av_score

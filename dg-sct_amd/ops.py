@@ -1184,3 +1184,97 @@ def _patch_merge_train(x, weight, ln_w, ln_b, eps, H, W, mode, lib=None, cached=
         with torch.no_grad():
             cached = (weight.detach().to(torch.bfloat16).contiguous(), ln_w.detach().float().contiguous(), ln_b.detach().float().contiguous())
     return _PatchMergeTrainFn.apply(lib, x.contiguous(), weight, ln_w, ln_b, *cached, float(eps), int(H), int(W), int(mode))
+
+
+# ---- the live part of the CMBS event head (csrc/head.hip) -----------------------------------------------------------------------
+CMBS_TOPK, CMBS_MAX_T, CMBS_MAX_D, CMBS_MAX_K = 4, 32, 512, 32
+
+
+class _CMBSHeadFn(torch.autograd.Function):
+    """(v, a, video_cas.{weight, bias}, audio_cas.{weight, bias}, classifier.{weight, bias}, event_classifier.{weight, bias}) ->
+    (is_event_scores [T, B, 1], event_scores [B, K], av_score [B, K]): one HIP launch forward, two backward (csrc/head.hip)."""
+
+    @staticmethod
+    def forward(ctx, lib, gamma, v, a, Wvc, bvc, Wac, bac, wc, bc, We, be):
+        T, B, D = v.shape
+        K = Wvc.shape[0]
+        dev = v.device
+        v, a = v.contiguous().float(), a.contiguous().float()
+        ps = [t.detach().contiguous().float() for t in (Wvc, bvc, Wac, bac, wc, bc, We, be)]
+        f32 = dict(dtype=torch.float32, device=dev)
+        is_event, event, av = torch.empty(T, B, 1, **f32), torch.empty(B, K, **f32), torch.empty(B, K, **f32)
+        topmask = torch.empty(B, 2, K, dtype=torch.int32, device=dev)
+        argmax = torch.empty(B, D, dtype=torch.int32, device=dev)
+        _mark_stream_use(v, a, *ps)
+        with _dev_guard(v):
+            lib.cmbs_head_forward(T, B, D, K, float(gamma), v.data_ptr(), a.data_ptr(), *[t.data_ptr() for t in ps], is_event.data_ptr(),
+                                  event.data_ptr(), av.data_ptr(), topmask.data_ptr(), argmax.data_ptr(), _stream_of(v))
+        ctx.lib, ctx.gamma, ctx.dims = lib, float(gamma), (T, B, D, K)
+        ctx.param_shapes = tuple((t.shape, t.dtype) for t in (Wvc, bvc, Wac, bac, wc, bc, We, be))
+        ctx.save_for_backward(v, a, ps[0], ps[2], ps[4], ps[6], topmask, argmax)
+        ctx.mark_non_differentiable(topmask, argmax)
+        ctx.set_materialize_grads(False)                   # an unused output's cotangent arrives as None -> a NULL pointer, no zero fill
+        return is_event, event, av, topmask, argmax
+
+    @staticmethod
+    def backward(ctx, d_is, d_ev, d_av, _dm, _da):
+        v, a, Wvc, Wac, wc, We, topmask, argmax = ctx.saved_tensors
+        T, B, D, K = ctx.dims
+        dev = v.device
+        need = ctx.needs_input_grad
+        if d_is is None and d_ev is None and d_av is None:
+            return (None,) * 12
+        cots = [t.contiguous().float() if t is not None else None for t in (d_is, d_ev, d_av)]
+        f32 = dict(dtype=torch.float32, device=dev)
+        want_x = need[2] or need[3]
+        dv, da = (torch.empty(T, B, D, **f32), torch.empty(T, B, D, **f32)) if want_x else (None, None)
+        grads = ws = None
+        if any(need[4:12]):                                # (all eight are computed together; the ones not asked for are dropped below)
+            grads = [torch.empty(s, **f32) for s in ((K, D), (K,), (K, D), (K,), (1, D), (1,), (K, D), (K,))]
+            ws = torch.empty(ctx.lib.cmbs_head_ws_bytes(T, B, D, K), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        _mark_stream_use(v, a, Wvc, Wac, wc, We, topmask, argmax, *cots)
+        with _dev_guard(v):
+            ctx.lib.cmbs_head_backward(T, B, D, K, ctx.gamma, v.data_ptr(), a.data_ptr(), Wvc.data_ptr(), Wac.data_ptr(), wc.data_ptr(),
+                                       We.data_ptr(), topmask.data_ptr(), argmax.data_ptr(), *[ptr(t) for t in cots], ptr(dv), ptr(da),
+                                       [g.data_ptr() for g in grads] if grads is not None else None, ptr(ws), _stream_of(v))
+        out = [None, None, dv if need[2] else None, da if need[3] else None]
+        for i, (shape, dtype) in enumerate(ctx.param_shapes):
+            out.append(grads[i].view(shape).to(dtype) if grads is not None and need[4 + i] else None)
+        return tuple(out)
+
+
+def cmbs_head_supported(v: torch.Tensor, a: torch.Tensor, K: int) -> bool:
+    """the kernels take these inputs: fp32 [T, B, D] on a ROCm device inside the limits of include/dgsct.h"""
+    if not (isinstance(v, torch.Tensor) and isinstance(a, torch.Tensor) and v.dim() == 3 and v.shape == a.shape):
+        return False
+    T, B, D = v.shape
+    return (v.is_cuda and a.device == v.device and v.dtype == torch.float32 and a.dtype == torch.float32 and CMBS_TOPK <= T <= CMBS_MAX_T
+            and B >= 1 and D % 64 == 0 and 64 <= D <= CMBS_MAX_D and 1 <= K <= CMBS_MAX_K)
+
+
+def cmbs_head(v: torch.Tensor, a: torch.Tensor, video_cas_w, video_cas_b, audio_cas_w, audio_cas_b, cls_w, cls_b, event_w, event_b,
+              gamma: float, lib: Optional[Lib] = None, return_saved: bool = False):
+    """The live part of ``CMBS.forward`` (net_trans.py:273-292) on fp32 time-major ``v``, ``a`` [T, B, D]: returns
+    ``(is_event_scores [T, B, 1], event_scores [B, K], av_score [B, K])``; with ``return_saved`` also the two tensors the backward reads
+    instead of a sort permutation, ``topmask [B, 2, K]`` and ``argmax [B, D]`` (int32).  Shapes outside the limits are refused by the
+    launcher (nothing is launched); a library without the export raises naming the symbol.  No CPU kernels."""
+    if not (isinstance(v, torch.Tensor) and isinstance(a, torch.Tensor) and v.dim() == 3 and v.shape == a.shape):
+        raise RuntimeError("dg-sct_amd: cmbs_head takes v, a of one shape [T, B, D]")
+    if v.dtype != torch.float32 or a.dtype != torch.float32:
+        raise RuntimeError(f"dg-sct_amd: cmbs_head runs in fp32, as the reference runs this head (got {v.dtype}, {a.dtype})")
+    if lib is None:
+        if not v.is_cuda:
+            raise RuntimeError("dg-sct_amd: cmbs_head runs on MI355X through libdgsct.so; there is no CPU path (CMBS(fused=False) is the "
+                               "ATen formulation)")
+        lib = _lib.default_lib()
+    if not lib.has_cmbs_head():
+        raise RuntimeError(f"dg-sct_amd: {lib.path} does not export dgsct_cmbs_head_forward (a library without the CMBS event head)")
+    K, D = video_cas_w.shape
+    for name, t, n in (("video_cas.weight", video_cas_w, K * D), ("video_cas.bias", video_cas_b, K), ("audio_cas.weight", audio_cas_w, K * D),
+                       ("audio_cas.bias", audio_cas_b, K), ("classifier.weight", cls_w, D), ("classifier.bias", cls_b, 1),
+                       ("event_classifier.weight", event_w, K * D), ("event_classifier.bias", event_b, K)):
+        if t.numel() != n or t.device != v.device or D != v.shape[-1]:
+            raise RuntimeError(f"dg-sct_amd: cmbs_head: {name} must hold {n} elements on {v.device} for D = {v.shape[-1]}, K = {K}")
+    outs = _CMBSHeadFn.apply(lib, float(gamma), v, a, video_cas_w, video_cas_b, audio_cas_w, audio_cas_b, cls_w, cls_b, event_w, event_b)
+    return outs if return_saved else outs[:3]

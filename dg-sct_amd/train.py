@@ -58,6 +58,30 @@ def trainable_by_name(named_parameters: Iterable[Tuple[str, torch.nn.Parameter]]
     return groups
 
 
+def ave_loss(is_event_scores: torch.Tensor, event_scores: torch.Tensor, audio_visual_gate: torch.Tensor, av_score: torch.Tensor,
+             labels: torch.Tensor) -> torch.Tensor:
+    """The four-term loss of the reference's AVE training loop (``main_trans.py:113-130``) on what ``AVENet`` / ``forward_swin`` return:
+    ``is_event_scores`` / ``audio_visual_gate`` [T, B, 1], ``event_scores`` / ``av_score`` [B, 28], ``labels`` [B, T, 29] (one-hot per frame,
+    the last class is background).
+
+        labels_BCE [B, T]  = 1 where the frame carries a foreground class        labels_event [B] = the clip's foreground class
+        loss = BCEWithLogits(is_event^T, labels_BCE) + BCEWithLogits(gate^T, labels_BCE)
+             + CrossEntropy(event_scores, labels_event) + CrossEntropy(av_score, labels_event)              (all mean-reduced)
+
+    ``audio_visual_gate`` is already a product of two sigmoids, and the reference feeds it to the LOGITS loss all the same
+    (``criterion(audio_visual_gate, labels_BCE)`` with ``criterion = BCEWithLogitsLoss``): kept as it is, because parity with the
+    reference's training signal is the contract.  A clip whose frames are all background gets ``labels_event`` 0, as the reference's
+    ``max`` over an all-zero row gives it."""
+    F = torch.nn.functional
+    is_event = is_event_scores.transpose(1, 0).squeeze(-1).contiguous()
+    gate = audio_visual_gate.transpose(1, 0).squeeze(-1).contiguous()
+    labels_bce, labels_evn = labels[:, :, :-1].max(-1)
+    labels_event, _ = labels_evn.max(-1)
+    labels_bce = labels_bce.to(is_event.dtype)
+    return (F.binary_cross_entropy_with_logits(is_event, labels_bce) + F.binary_cross_entropy_with_logits(gate, labels_bce)
+            + F.cross_entropy(event_scores, labels_event) + F.cross_entropy(av_score, labels_event))
+
+
 def make_optimizer(model: torch.nn.Module, lr: float = 5e-4, lr_mlp: float = 5e-6, decay: float = 0.35, decay_epoch: int = 3,
                    is_vit_ln: bool = False, fused: Optional[bool] = None, task: str = "ave"):
     groups = trainable_by_name(model.named_parameters(), is_vit_ln, lr, lr_mlp, task=task)

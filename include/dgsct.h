@@ -353,6 +353,32 @@ int dgsct_temporal_gate_backward(int R, int D, float gamma, const float* akv, co
                                  const float* dOa, const float* dg, float* dakv, float* dvkv, float* dvq, float* daq, float* dwa,
                                  float* dba, float* dwv, float* dbv, void* stream);
 
+/* ---- the live part of the CMBS event head (csrc/head.hip; DG-SCT/AVE/nets/net_trans.py:254-292 and :116-138) ---------------------
+ * Optional exports, like the front ends and the patch merging (still DGSCT_VERSION 101): bind them by name.
+ * Everything fp32.  v, a [T][B][D] time-major (as dgsct_temporal_gate_forward writes out_v / out_a); parameters in the reference's layout:
+ * Wvc, Wac [K][D] / bvc, bac [K] (video_cas, audio_cas), wc [D] / bc [1] (localize_module.classifier), We [K][D] / be [K]
+ * (localize_module.event_classifier).
+ *   cas_m[t,b,k] = W_m[k] . x_m[t,b] + b_m[k];   s_m[b,k] = mean of the 4 largest of cas_m[:,b,k] over t;   av = (s_v + s_a) / 2
+ *   f = (v + a) / 2;   is_event[t,b] = wc . f[t,b] + bc;   event[b,k] = We[k] . max_t f[t,b] + be[k] + gamma * av[b,k]
+ * forward (ONE launch, one workgroup per clip): is_event [T][B], event [B][K], av [B][K], and for the backward topmask [B][2][K] int32
+ *   (video, audio; bit t set: timestep t is one of the four selected, ties to the earlier timestep) and argmax [B][D] int32 (the first t
+ *   attaining the max).
+ * backward (TWO launches): cotangents d_is [T][B], d_ev [B][K], d_av [B][K], each may be NULL (= zero).  dv, da [T][B][D]: both or both
+ *   NULL.  The eight parameter gradients (dWvc [K][D], dbvc [K], dWac, dbac, dwc [D], dbc [1], dWe [K][D], dbe [K]) are OVERWRITTEN, all
+ *   eight or all NULL (a frozen head: that work, v, a and ws are then not needed and may be NULL).  Every workgroup sums the clips it owns
+ *   into its own row of `ws` (dgsct_cmbs_head_ws_bytes(...) bytes) and a second kernel adds the rows in a fixed order: no atomics, the
+ *   gradients are bit-identical from call to call.
+ * Limits: top-k fixed at 4; 4 <= T <= 32; D a multiple of 64, <= 512; 1 <= K <= 32; v, a, the weight matrices and ws 16-byte aligned.
+ * Asynchronous on `stream`; 0 or an error code (dgsct_cmbs_head_ws_bytes: -1). */
+int64_t dgsct_cmbs_head_ws_bytes(int T, int B, int D, int K);
+int dgsct_cmbs_head_forward(int T, int B, int D, int K, float gamma, const float* v, const float* a, const float* Wvc, const float* bvc,
+                            const float* Wac, const float* bac, const float* wc, const float* bc, const float* We, const float* be,
+                            float* is_event, float* event, float* av, int32_t* topmask, int32_t* argmax, void* stream);
+int dgsct_cmbs_head_backward(int T, int B, int D, int K, float gamma, const float* v, const float* a, const float* Wvc, const float* Wac,
+                             const float* wc, const float* We, const int32_t* topmask, const int32_t* argmax, const float* d_is,
+                             const float* d_ev, const float* d_av, float* dv, float* da, float* dWvc, float* dbvc, float* dWac, float* dbac,
+                             float* dwc, float* dbc, float* dWe, float* dbe, void* ws, void* stream);
+
 /* Per-frame scalar gate on a feature block: the tail of the AVVP / AVS copies of TemporalAttention
  * (`x + gate * x * gamma` with one gate per frame: AVVP/nets/mgn.py:155-156 on [B*10][128] features,
  * avs_s4/model/PVT_AVSModel.py:572-577 on the four [B*5][256][H][W] decoder maps).
