@@ -157,6 +157,13 @@ class Lib:
             self._patch_embed_pws.restype = C.c_int64
         if self._patch_embed_bwd_params is not None:
             self._patch_embed_bwd_params.argtypes = [C.c_int] * 9 + [C.c_void_p] * 8 + [C.c_float] + [C.c_void_p] * 8
+        # optional (include/dgsct.h): the audio mode of both with SpecAugment stripes and mix-up folded into the loads
+        self._patch_embed_aug = getattr(c, "dgsct_patch_embed_forward_aug", None)
+        self._patch_embed_bwd_params_aug = getattr(c, "dgsct_patch_embed_backward_params_aug", None)
+        if self._patch_embed_aug is not None:
+            self._patch_embed_aug.argtypes = [C.c_int] * 4 + [C.c_void_p] * 9 + [C.c_float] + [C.c_void_p] * 2
+        if self._patch_embed_bwd_params_aug is not None:
+            self._patch_embed_bwd_params_aug.argtypes = [C.c_int] * 4 + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 8
         # optional (include/dgsct.h): patch merging between two stages (csrc/pmerge.hip); the host emulation lacks it
         self._pmerge_ws = getattr(c, "dgsct_patch_merge_ws_bytes", None)
         self._pmerge_fwd = getattr(c, "dgsct_patch_merge_forward", None)
@@ -318,6 +325,23 @@ class Lib:
         self._check(self._front_end(self._patch_embed_bwd_params, "dgsct_patch_embed_backward_params")(
             mode, in_dtype, dout_dtype, B, in_chans, H, W, T, C_, x, bn_scale, bn_shift, bn_pivot, w, b, ln_w, ln_b, eps, dout, dw, db, dln_w,
             dln_b, dbn, ws, stream), "dgsct_patch_embed_backward_params")
+
+    def has_patch_embed_aug(self) -> bool:
+        """whether this library exports dgsct_patch_embed_forward_aug / dgsct_patch_embed_backward_params_aug (audio mode with the
+        SpecAugment stripes and the mix-up inside the kernels) on top of the parameter-gradient backward"""
+        return self.has_patch_embed_params() and None not in (self._patch_embed_aug, self._patch_embed_bwd_params_aug)
+
+    def patch_embed_forward_aug(self, out_dtype, B, T, C_, logmel, bn_scale, bn_shift, stripes, lam, w, b, ln_w, ln_b, eps, out, stream):
+        """stripes int32 [B, 4, 2] / lam fp32 [B] device pointers or None (include/dgsct.h: dgsct_patch_embed_forward_aug)"""
+        self._check(self._front_end(self._patch_embed_aug, "dgsct_patch_embed_forward_aug")(
+            out_dtype, B, T, C_, logmel, bn_scale, bn_shift, stripes, lam, w, b, ln_w, ln_b, eps, out, stream), "dgsct_patch_embed_forward_aug")
+
+    def patch_embed_backward_params_aug(self, dout_dtype, B, T, C_, logmel, bn_scale, bn_shift, bn_pivot, stripes, lam, w, b, ln_w, ln_b, eps,
+                                        dout, dw, db, dln_w, dln_b, dbn, ws, stream):
+        """the outputs and the workspace of `patch_embed_backward_params` in audio mode (include/dgsct.h: dgsct_patch_embed_backward_params_aug)"""
+        self._check(self._front_end(self._patch_embed_bwd_params_aug, "dgsct_patch_embed_backward_params_aug")(
+            dout_dtype, B, T, C_, logmel, bn_scale, bn_shift, bn_pivot, stripes, lam, w, b, ln_w, ln_b, eps, dout, dw, db, dln_w, dln_b, dbn, ws,
+            stream), "dgsct_patch_embed_backward_params_aug")
 
     @property
     def has_patch_merge(self) -> bool:

@@ -22,6 +22,11 @@
 //                  the convolution and the LayerNorm statistics are recomputed from x (the forward stores nothing for it), the sums stay in
 //                  registers across the grid-stride loop, the four waves meet in LDS, each workgroup stores one partial row and
 //                  patch_embed_bwd_sum_k adds the rows in a fixed order: no atomics, bit-identical from call to call.
+//   AUG = true     (audio mode) the train-time augmentation of htsat.py:451 / nets/utils.py:143-153 between `bn0` and the stretch, inside
+//                  the same loads: `spec_augmenter` (two time and two mel stripes per sample set to 0) is a zero at a tap, `do_mixup`
+//                  (lam[b] x[b] + (1 - lam[b]) x[B-1-b]) a second tap from the mirrored sample.  fe_pixels then returns the pair (R, K)
+//                  with pixel = scale R + shift K; without augmentation K is 1.  Ownership, grid, workspace and summation order are
+//                  those of the plain kernels, which the AUG = false instantiations remain.
 //
 // The extern "C" entry points live here (not in capi.cpp): the host emulation of the CPU tests links capi.cpp against host
 // primitives and has no front end.
@@ -184,6 +189,9 @@ struct PatchArgs {
   int H, W, Hp, Wp, C, T;
   long tokens;                             // B * Hp * Wp
   float eps, tscale;                       // tscale = (T - 1) / 1023 (bicubic, align_corners)
+  const int* stripes;                      // AUG: [B][4][2] (begin, end) half-open; rows 0, 1 over the T frames, rows 2, 3 over the mel bins (NULL: none)
+  const float* lam;                        // AUG: [B], sample b becomes lam[b] x[b] + (1 - lam[b]) x[B-1-b] (NULL: no mix-up)
+  int B;
 };
 
 // PyTorch's cubic convolution coefficients (A = -0.75) for the taps at -1, 0, +1, +2 around floor(src), fraction t
@@ -196,15 +204,29 @@ __device__ __forceinline__ void fe_cubic(float t, float (&c)[4]) {
   c[3] = ((A * d - 5.f * A) * d + 8.f * A) * d - 4.f * A;
 }
 
+// One sample's stripes (AUG): whether mel bin f / frame t survives them.  The values are only ever compared with indices, so a table
+// with entries outside its axis is harmless here (the callers refuse it all the same).
+struct FeStripes {
+  int s[8];
+  __device__ __forceinline__ void load(const int* tab, long b) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s[i] = tab ? tab[b * 8 + i] : 0;
+  }
+  __device__ __forceinline__ bool mel(int f) const { return !((f >= s[4] && f < s[5]) || (f >= s[6] && f < s[7])); }
+  __device__ __forceinline__ bool frame(int t) const { return !((t >= s[0] && t < s[1]) || (t >= s[2] && t < s[3])); }
+};
+
 // The pixels (row r, column dx) of token `tok`, one per input channel, as the convolution sees them (0 past the last token).  Audio mode:
 // the bicubic stretch and the fold are the address arithmetic, `bn0` the scale / shift; `raw` is the stretched log-mel before `bn0` and
-// f its mel bin (what the `bn0` gradients are collected over).
-template <int IC, bool AUDIO>
-__device__ __forceinline__ void fe_pixels(const PatchArgs& p, long tok, int r, int dx, float (&v)[IC], float& raw, int& f) {
+// f its mel bin (what the `bn0` gradients are collected over).  AUG: with keep_b(t, f) = 0 inside a stripe of sample b, b' = B - 1 - b,
+//   raw = R = sum_e cf_e (lam_b keep_b lm[b] + (1 - lam_b) keep_b' lm[b']),   kk = K = sum_e cf_e (lam_b keep_b + (1 - lam_b) keep_b')
+// over the clamped taps e, and the pixel is scale R + shift K (not AUG: kk = 1 and the pixel is scale raw + shift).
+template <int IC, bool AUDIO, bool AUG = false>
+__device__ __forceinline__ void fe_pixels(const PatchArgs& p, long tok, int r, int dx, float (&v)[IC], float& raw, float& kk, int& f) {
   const long P = (long)p.Hp * p.Wp;
 #pragma unroll
   for (int ch = 0; ch < IC; ++ch) v[ch] = 0.f;
-  raw = 0.f; f = 0;
+  raw = 0.f; f = 0; kk = AUG ? 0.f : 1.f;
   if (tok < p.tokens) {
     const long b = tok / P;
     const int pi = (int)(tok - b * P), pr = pi / p.Wp, pc = pi - pr * p.Wp;
@@ -213,22 +235,61 @@ __device__ __forceinline__ void fe_pixels(const PatchArgs& p, long tok, int r, i
       const int tp = (pr >> 4) * 256 + 4 * pc + dx;                              // image[q*64 + f][t'] = logmel'[q*256 + t'][f]
       const float* lm = reinterpret_cast<const float*>(p.x) + b * (long)p.T * FE_NMEL + f;
       float val;
-      if (p.T == FE_MAX_T) val = lm[(long)tp * FE_NMEL];
-      else {
-        const float src = p.tscale * (float)tp, fl = floorf(src);
-        const int i0 = (int)fl;
-        float cf[4];
-        fe_cubic(src - fl, cf);
+      if (AUG) {
+        const bool mix = p.lam != nullptr;
+        // the four tokens of a group lie in one sample (4096 tokens each): b is wave-uniform, and saying so keeps lam and the two stripe
+        // tables in scalar registers, fetched by scalar loads
+        const long bu = (long)__builtin_amdgcn_readfirstlane((int)b), b2 = (long)p.B - 1 - bu;
+        const float la = mix ? p.lam[bu] : 1.f, lb = 1.f - la;
+        const float* lm2 = reinterpret_cast<const float*>(p.x) + b2 * (long)p.T * FE_NMEL + f;
+        FeStripes sa, sb;
+        sa.load(p.stripes, bu);
+        sb.load(mix ? p.stripes : nullptr, b2);
+        const bool ma = sa.mel(f), mb = sb.mel(f);
+        float cf[4] = {1.f, 0.f, 0.f, 0.f};
+        int i0 = tp + 1, ne = 1;                                                 // T == 1024: the one tap tp with weight 1
+        if (p.T != FE_MAX_T) {
+          const float src = p.tscale * (float)tp, fl = floorf(src);
+          i0 = (int)fl; ne = 4;
+          fe_cubic(src - fl, cf);
+        }
         val = 0.f;
+        float ks = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          int ii = i0 - 1 + e;
-          ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
-          val += cf[e] * lm[(long)ii * FE_NMEL];
+          if (e < ne) {
+            int ii = i0 - 1 + e;
+            ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
+            const bool ka = ma && sa.frame(ii);
+            float x = la * (ka ? lm[(long)ii * FE_NMEL] : 0.f), k = ka ? la : 0.f;
+            if (mix) {
+              const bool kb = mb && sb.frame(ii);
+              x += lb * (kb ? lm2[(long)ii * FE_NMEL] : 0.f);
+              k += kb ? lb : 0.f;
+            }
+            val += cf[e] * x; ks += cf[e] * k;
+          }
         }
+        raw = val; kk = ks;
+        v[0] = val * p.bn_scale[f] + ks * p.bn_shift[f];
+      } else {
+        if (p.T == FE_MAX_T) val = lm[(long)tp * FE_NMEL];
+        else {
+          const float src = p.tscale * (float)tp, fl = floorf(src);
+          const int i0 = (int)fl;
+          float cf[4];
+          fe_cubic(src - fl, cf);
+          val = 0.f;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            int ii = i0 - 1 + e;
+            ii = ii < 0 ? 0 : (ii > p.T - 1 ? p.T - 1 : ii);
+            val += cf[e] * lm[(long)ii * FE_NMEL];
+          }
+        }
+        raw = val;
+        v[0] = val * p.bn_scale[f] + p.bn_shift[f];
       }
-      raw = val;
-      v[0] = val * p.bn_scale[f] + p.bn_shift[f];
     } else {
 #pragma unroll
       for (int ch = 0; ch < IC; ++ch)
@@ -237,7 +298,7 @@ __device__ __forceinline__ void fe_pixels(const PatchArgs& p, long tok, int r, i
   }
 }
 
-template <int IC, bool AUDIO, int NJ>
+template <int IC, bool AUDIO, int NJ, bool AUG = false>
 __global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
   constexpr int K = IC * 16;
   __shared__ float Wt[K * NJ * 64];                // [k][c], c < C (rows packed at pitch C)
@@ -262,9 +323,9 @@ __global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
   const float invC = 1.f / (float)C;
   for (long grp = (long)blockIdx.x * 4 + (threadIdx.x >> 6); grp < ngroups; grp += (long)gridDim.x * 4) {
     const long tok0 = grp * 4, tok = tok0 + tt;
-    float v[IC], raw;
+    float v[IC], raw, kk;
     int f;
-    fe_pixels<IC, AUDIO>(p, tok, r, dx, v, raw, f);
+    fe_pixels<IC, AUDIO, AUG>(p, tok, r, dx, v, raw, kk, f);
     float acc[4][NJ];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -302,19 +363,19 @@ __global__ __launch_bounds__(256) void patch_embed_k(const PatchArgs p) {
   }
 }
 
-template <int IC, bool AUDIO, int NJ>
+template <int IC, bool AUDIO, int NJ, bool AUG = false>
 static void patch_embed_launch(const PatchArgs& a, hipStream_t s) {
-  const void* fn = reinterpret_cast<const void*>(&patch_embed_k<IC, AUDIO, NJ>);
+  const void* fn = reinterpret_cast<const void*>(&patch_embed_k<IC, AUDIO, NJ, AUG>);
   const long want = ((a.tokens + 3) / 4 + 3) / 4;
   const long cap = wg_capacity(fn, 0);
-  hipLaunchKernelGGL((patch_embed_k<IC, AUDIO, NJ>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((patch_embed_k<IC, AUDIO, NJ, AUG>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, a);
 }
-template <int IC, bool AUDIO>
+template <int IC, bool AUDIO, bool AUG = false>
 static void patch_embed_nj(const PatchArgs& a, hipStream_t s) {
   const int nj = (a.C + 63) / 64;
-  if (nj == 1) patch_embed_launch<IC, AUDIO, 1>(a, s);
-  else if (nj == 2) patch_embed_launch<IC, AUDIO, 2>(a, s);
-  else patch_embed_launch<IC, AUDIO, 3>(a, s);
+  if (nj == 1) patch_embed_launch<IC, AUDIO, 1, AUG>(a, s);
+  else if (nj == 2) patch_embed_launch<IC, AUDIO, 2, AUG>(a, s);
+  else patch_embed_launch<IC, AUDIO, 3, AUG>(a, s);
 }
 
 // ---- patch embedding: parameter gradients ------------------------------------------------------------------------------------------
@@ -338,7 +399,9 @@ struct PatchBwdArgs {
 // adds them to its 2 x 64 bins in LDS.  Everything else stays in registers across the grid-stride loop; at the end the four waves add
 // their registers into one [K + 3][C] LDS buffer one after the other (a fixed order) and the workgroup stores ONE row of the workspace.
 // No atomics: the result depends on the grid alone.
-template <int IC, bool AUDIO, int NJ>
+// AUG: the pixel is scale R + shift K, so g1 is collected over R - pivot K and g0 over K; the per-row shortcut of g0 above (sum_dx W, K = 1)
+// becomes the sum weighted by K[r][dx], formed like g1's.  The recomputed convolution sees the augmented pixels.
+template <int IC, bool AUDIO, int NJ, bool AUG = false>
 __global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
   constexpr int K = IC * 16, KR = K + 3;
   __shared__ float sm[KR * NJ * 64];               // the weights [k][c] at pitch C during the loop, the combined sums [K + 3][C] after it
@@ -363,7 +426,7 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
   }
   __syncthreads();
   float wrow[4][NJ];                               // audio: sum_dx W[4r + dx][c]
-  if (AUDIO) {
+  if (AUDIO && !AUG) {
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
@@ -382,10 +445,10 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
   const float invC = 1.f / (float)C;
   for (long grp = (long)blockIdx.x * 4 + wave; grp < ngroups; grp += (long)gridDim.x * 4) {
     const long tok0 = grp * 4;
-    float v[IC], raw;
+    float v[IC], raw, kk;
     int f;
-    fe_pixels<IC, AUDIO>(p, tok0 + tt, r, dx, v, raw, f);
-    const float sv = AUDIO ? raw - a.pivot[f] : 0.f;
+    fe_pixels<IC, AUDIO, AUG>(p, tok0 + tt, r, dx, v, raw, kk, f);
+    const float sv = AUDIO ? (AUG ? raw - a.pivot[f] * kk : raw - a.pivot[f]) : 0.f;
     float g[4][NJ];                                // dOut of the four tokens, in flight while the convolution is recomputed
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -443,15 +506,15 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
         for (int j = 0; j < NJ; ++j) acc[t][j] = 0.f;
       }
     }
-    float p1[4] = {0.f, 0.f, 0.f, 0.f};
+    float p1[4] = {0.f, 0.f, 0.f, 0.f}, p0[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ch = 0; ch < IC; ++ch)
 #pragma unroll
       for (int rd = 0; rd < 16; ++rd) {
         const int k = ch * 16 + rd;
-        float u[NJ];                               // audio: sum_t dconv[t][c] s[t][rd]
+        float u[NJ], uk[NJ];                       // audio: sum_t dconv[t][c] s[t][rd]  (AUG: and sum_t dconv[t][c] K[t][rd])
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) u[j] = 0.f;
+        for (int j = 0; j < NJ; ++j) { u[j] = 0.f; uk[j] = 0.f; }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int src = (rd >> 2) * 16 + t * 4 + (rd & 3);
@@ -462,20 +525,30 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_k(const PatchBwdArgs a) {
             const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sv), src));
 #pragma unroll
             for (int j = 0; j < NJ; ++j) u[j] += sx * acc[t][j];
+            if (AUG) {
+              const float kx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kk), src));
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) uk[j] += kx * acc[t][j];
+            }
           }
         }
         if (AUDIO) {
 #pragma unroll
           for (int j = 0; j < NJ; ++j) p1[rd >> 2] += u[j] * sm[k * C + cw[j]];
+          if (AUG) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) p0[rd >> 2] += uk[j] * sm[k * C + cw[j]];
+          }
         }
       }
     if (AUDIO) {
-      float p0[4] = {0.f, 0.f, 0.f, 0.f};
+      if (!AUG) {
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float ds = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
+        for (int j = 0; j < NJ; ++j) {
+          const float ds = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) p0[rr] += ds * wrow[rr][j];
+          for (int rr = 0; rr < 4; ++rr) p0[rr] += ds * wrow[rr][j];
+        }
       }
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) group_sum2(p1[rr], p0[rr], 64);
@@ -547,20 +620,20 @@ static long pe_bwd_rows(long tokens) {
   const long want = ((tokens + 3) / 4 + 3) / 4;
   return want < PE_BWD_MAX_WG ? want : PE_BWD_MAX_WG;
 }
-template <int IC, bool AUDIO, int NJ>
+template <int IC, bool AUDIO, int NJ, bool AUG = false>
 static void patch_embed_bwd_launch(PatchBwdArgs& a, float* dw, float* db, float* dlw, float* dlb, float* dbn, hipStream_t s) {
-  const void* fn = reinterpret_cast<const void*>(&patch_embed_bwd_k<IC, AUDIO, NJ>);
+  const void* fn = reinterpret_cast<const void*>(&patch_embed_bwd_k<IC, AUDIO, NJ, AUG>);
   const long rows = pe_bwd_rows(a.f.tokens), cap = wg_capacity(fn, 0);
   const int grid = (int)(rows < cap ? rows : cap);                   // <= the rows the workspace holds
-  hipLaunchKernelGGL((patch_embed_bwd_k<IC, AUDIO, NJ>), dim3(grid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((patch_embed_bwd_k<IC, AUDIO, NJ, AUG>), dim3(grid), dim3(256), 0, s, a);
   hipLaunchKernelGGL(patch_embed_bwd_sum_k, dim3((a.rs + 15) / 16), dim3(256), 0, s, (const float*)a.ws, grid, a.rs, IC * 16, a.f.C, dw, db, dlw, dlb, dbn);
 }
-template <int IC, bool AUDIO>
+template <int IC, bool AUDIO, bool AUG = false>
 static void patch_embed_bwd_nj(PatchBwdArgs& a, float* dw, float* db, float* dlw, float* dlb, float* dbn, hipStream_t s) {
   const int nj = (a.f.C + 63) / 64;
-  if (nj == 1) patch_embed_bwd_launch<IC, AUDIO, 1>(a, dw, db, dlw, dlb, dbn, s);
-  else if (nj == 2) patch_embed_bwd_launch<IC, AUDIO, 2>(a, dw, db, dlw, dlb, dbn, s);
-  else patch_embed_bwd_launch<IC, AUDIO, 3>(a, dw, db, dlw, dlb, dbn, s);
+  if (nj == 1) patch_embed_bwd_launch<IC, AUDIO, 1, AUG>(a, dw, db, dlw, dlb, dbn, s);
+  else if (nj == 2) patch_embed_bwd_launch<IC, AUDIO, 2, AUG>(a, dw, db, dlw, dlb, dbn, s);
+  else patch_embed_bwd_launch<IC, AUDIO, 3, AUG>(a, dw, db, dlw, dlb, dbn, s);
 }
 
 static int fe_logmel_wgs(int B, int64_t L) {
@@ -614,6 +687,7 @@ static bool fe_patch_check(const char* who, int mode, int in_dtype, int tok_dtyp
   if (mode == DGSCT_PATCH_AUDIO) { a.T = T; a.tscale = (float)(T - 1) / (float)(FE_MAX_T - 1); }
   a.H = H; a.W = W; a.Hp = H / 4; a.Wp = W / 4;
   a.tokens = (long)B * a.Hp * a.Wp;
+  a.B = B;
   return true;
 }
 static long pe_bwd_row_floats(int mode, int in_chans, int C) { return (long)(in_chans * 16 + 3) * C + (mode == DGSCT_PATCH_AUDIO ? 2 * FE_NMEL : 0); }
@@ -663,6 +737,24 @@ int dgsct_patch_embed_forward(int mode, int in_dtype, int out_dtype, int B, int 
   return has_error() ? 1 : 0;
 }
 
+int dgsct_patch_embed_forward_aug(int out_dtype, int B, int T, int C, const float* logmel, const float* bn_scale, const float* bn_shift,
+                                  const int32_t* stripes, const float* lam, const float* weight, const float* bias, const float* ln_weight,
+                                  const float* ln_bias, float eps, void* out, void* stream) {
+  clear_error();
+  const char* who = "dgsct_patch_embed_forward_aug";
+  if (!out) { set_error("%s: NULL argument", who); return 2; }
+  PatchArgs a{};
+  if (!fe_patch_check(who, DGSCT_PATCH_AUDIO, DGSCT_F32, out_dtype, B, 1, 256, 256, T, C, logmel, bn_scale, bn_shift, weight, bias, ln_weight, ln_bias,
+                      eps, a)) return 2;
+  a.out = out; a.odt = out_dtype; a.stripes = (const int*)stripes; a.lam = lam;
+  hipStream_t s = (hipStream_t)stream;
+  clear_async();
+  if (stripes || lam) patch_embed_nj<1, true, true>(a, s);
+  else patch_embed_nj<1, true>(a, s);
+  check_async(who);
+  return has_error() ? 1 : 0;
+}
+
 int64_t dgsct_patch_embed_params_ws_floats(int mode, int B, int in_chans, int H, int W, int C) {
   clear_error();
   const char* who = "dgsct_patch_embed_params_ws_floats";
@@ -687,6 +779,27 @@ int dgsct_patch_embed_backward_params(int mode, int in_dtype, int dout_dtype, in
   if (mode == DGSCT_PATCH_AUDIO) patch_embed_bwd_nj<1, true>(a, dweight, dbias, dln_weight, dln_bias, dbn, s);
   else if (in_chans == 1) patch_embed_bwd_nj<1, false>(a, dweight, dbias, dln_weight, dln_bias, nullptr, s);
   else patch_embed_bwd_nj<3, false>(a, dweight, dbias, dln_weight, dln_bias, nullptr, s);
+  check_async(who);
+  return has_error() ? 1 : 0;
+}
+
+int dgsct_patch_embed_backward_params_aug(int dout_dtype, int B, int T, int C, const float* logmel, const float* bn_scale, const float* bn_shift,
+                                          const float* bn_pivot, const int32_t* stripes, const float* lam, const float* weight, const float* bias,
+                                          const float* ln_weight, const float* ln_bias, float eps, const void* dout, float* dweight, float* dbias,
+                                          float* dln_weight, float* dln_bias, float* dbn, float* ws, void* stream) {
+  clear_error();
+  const char* who = "dgsct_patch_embed_backward_params_aug";
+  if (!dout || !dweight || !dbias || !dln_weight || !dln_bias || !ws) { set_error("%s: NULL argument", who); return 2; }
+  if (!bn_pivot || !dbn) { set_error("%s: audio mode needs bn_pivot and dbn", who); return 2; }
+  PatchBwdArgs a{};
+  if (!fe_patch_check(who, DGSCT_PATCH_AUDIO, DGSCT_F32, dout_dtype, B, 1, 256, 256, T, C, logmel, bn_scale, bn_shift, weight, bias, ln_weight, ln_bias,
+                      eps, a.f)) return 2;
+  a.f.stripes = (const int*)stripes; a.f.lam = lam;
+  a.dout = dout; a.ddt = dout_dtype; a.pivot = bn_pivot; a.ws = ws; a.rs = (int)pe_bwd_row_floats(DGSCT_PATCH_AUDIO, 1, C);
+  hipStream_t s = (hipStream_t)stream;
+  clear_async();
+  if (stripes || lam) patch_embed_bwd_nj<1, true, true>(a, dweight, dbias, dln_weight, dln_bias, dbn, s);
+  else patch_embed_bwd_nj<1, true>(a, dweight, dbias, dln_weight, dln_bias, dbn, s);
   check_async(who);
   return has_error() ? 1 : 0;
 }

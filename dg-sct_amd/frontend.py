@@ -20,14 +20,25 @@ library lacks the export), ``fused=False`` / CPU is the ATen formulation under p
 ``_KERNELS_FASTER_TRAIN`` (the kinds measured faster, profiles/frontend_train_bench.txt).  With grad disabled, or with every one of those parameters frozen again, a
 trainable module runs exactly the frozen path.
 
+``spec_augment=True`` (HTSATFrontEnd) keeps the reference's train-time augmentation: ``spec_augmenter`` (htsat.py:451: torchlibrosa's
+``SpecAugmentation(time_drop_width=64, time_stripes_num=2, freq_drop_width=8, freq_stripes_num=2)``) zeroes two time and two mel stripes per
+sample of the ``bn0`` output, and ``do_mixup`` (nets/utils.py:143-153) then mixes sample b with sample B-1-b by ``mixup_lambda``
+(``forward(waveform, mixup_lambda, stripes)``), both before the stretch and both only in train mode (net_trans.py:862-866).  The stripes are
+drawn by ``draw_stripes`` from torch's CPU generator, draw for draw as the published ``DropStripes`` does; an explicit ``stripes=`` table
+replays a run.  On the kernel path both are part of the loads of ``patch_embed_k`` / ``patch_embed_bwd_k`` (a zero at a tap, a second tap from
+the mirrored sample: ``dgsct_patch_embed_forward_aug`` / ``dgsct_patch_embed_backward_params_aug``), so neither the ``bn0`` output nor the
+image exists in memory; ``fused=False`` / CPU multiplies by the keep mask and mixes with ``torch.flip`` in ATen.  ``fused=None`` with an
+augmentation active follows ``_KERNELS_FASTER_AUG``.  Parity with torchlibrosa's ``DropStripes`` is unpinned like the rest (next paragraph):
+the pin is to the published algorithm (tests/test_frontend_aug_cpu.py).
+
 **Parity against torchlibrosa / librosa is unpinned**: neither is installed here, and the oracle cannot import the front end of
 ``htsat.py``.  The pin is to the published formulas evaluated in float64 (tests/test_frontend_cpu.py, tests/test_frontend_gpu.py): the
 centred, reflect-padded, periodic-Hann STFT; librosa's default (Slaney-scale, Slaney-normalised) mel filterbank; PyTorch's bicubic
 kernel.  A real HTS-AT checkpoint supplies its own ``logmel_extractor.melW``, which replaces the one built here.
 
-Out of scope: ``spec_augmenter`` and ``do_mixup`` (train-time augmentation drawn from the host RNG), ``ape`` /
-``pos_drop`` (off / identity in every reference config), the random ``crop_wav`` branch (more than 1024 frames raises here).  Patch merging
-and the Swin-V2 final norm live in ``merging.py`` (``AVETrunk``)."""
+Out of scope: ``do_mixup_label`` (the label side of the mix-up belongs to the task's loss), ``ape`` /
+``pos_drop`` (off / identity in every reference config), the random ``crop_wav`` branch (more than 1024 frames raises here), image-side
+augmentation.  Patch merging and the Swin-V2 final norm live in ``merging.py`` (``AVETrunk``)."""
 from __future__ import annotations
 
 import math
@@ -107,6 +118,44 @@ def _train_through_kernels(fused: Optional[bool], x: torch.Tensor, lib, who: str
     return True
 
 
+# `fused=None` with an augmentation active (stripes and / or mixup_lambda, train mode) takes the kernels only for the kinds listed here:
+# "frozen" (forward only) | "train" (forward + backward of a trainable module), by the same rule on the rows of `tools/frontend_bench.py
+# --augment` (profiles/frontend_aug_bench.txt).  A call without augmentation never looks at it.
+_KERNELS_FASTER_AUG: frozenset = frozenset({"frozen", "train"})
+
+TIME_DROP_WIDTH, TIME_STRIPES, FREQ_DROP_WIDTH, FREQ_STRIPES = 64, 2, 8, 2          # htsat.py:451
+
+
+def draw_stripes(B: int, T: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The stripes `spec_augmenter` would drop from a [B, 1, T, 64] batch, as int32 [B, 4, 2] of half-open (begin, end): rows 0 and 1 the
+    time stripes (frames of the un-stretched log-mel), rows 2 and 3 the mel stripes.  The published DropStripes algorithm, draw for draw on
+    the CPU generator (None: torch's default one): the time dropper first, for samples 0 .. B-1 in order and twice per sample
+    ``distance = randint(0, drop_width)`` then ``bgn = randint(0, total_width - distance)``; the mel dropper follows the same way.
+    T < 64 raises: a distance of up to 63 frames can leave the second range empty."""
+    if T < TIME_DROP_WIDTH:
+        raise ValueError(f"dg-sct_amd: draw_stripes: {T} frames are fewer than the time drop width {TIME_DROP_WIDTH} (the reference's "
+                         f"randint(0, total_width - distance) can have an empty range)")
+    out = torch.zeros(B, 4, 2, dtype=torch.int32)
+    for row0, total, width, num in ((0, T, TIME_DROP_WIDTH, TIME_STRIPES), (TIME_STRIPES, N_MELS, FREQ_DROP_WIDTH, FREQ_STRIPES)):
+        for n in range(B):
+            for j in range(num):
+                distance = int(torch.randint(low=0, high=width, size=(1,), generator=generator)[0])
+                bgn = int(torch.randint(low=0, high=total - distance, size=(1,), generator=generator)[0])
+                out[n, row0 + j, 0], out[n, row0 + j, 1] = bgn, bgn + distance
+    return out
+
+
+def keep_mask(stripes: torch.Tensor, T: int) -> torch.Tensor:
+    """stripes int32 [B, 4, 2] -> bool [B, T, 64]: False inside any of a sample's stripes"""
+    s = stripes.long()
+    t = torch.arange(T, device=s.device).view(1, T, 1)
+    f = torch.arange(N_MELS, device=s.device).view(1, 1, N_MELS)
+    drop = torch.zeros(s.shape[0], T, N_MELS, dtype=torch.bool, device=s.device)
+    for r, idx in ((0, t), (1, t), (2, f), (3, f)):
+        drop = drop | ((idx >= s[:, r, 0].view(-1, 1, 1)) & (idx < s[:, r, 1].view(-1, 1, 1)))
+    return ~drop
+
+
 class PatchEmbed(nn.Module):
     """``PatchEmbed`` of timm 0.6.12 / layers.py:56-86 at patch 4, stride 4: ``norm(proj(x).flatten(2).transpose(1, 2))``; keys
     ``proj.{weight,bias}``, ``norm.{weight,bias}``.  Frozen and forward-only; trainable=True: the four parameters require grad and the forward
@@ -184,7 +233,8 @@ class HTSATFrontEnd(nn.Module):
     _DERIVED = ("spectrogram_extractor.stft.conv_real.weight", "spectrogram_extractor.stft.conv_imag.weight")
 
     def __init__(self, embed_dim: int = 96, spec_size: int = 256, sample_rate: int = 32000, fmin: float = 50, fmax: float = 14000,
-                 fused: Optional[bool] = None, lib=None, out_dtype: Optional[torch.dtype] = None, trainable: bool = False):
+                 fused: Optional[bool] = None, lib=None, out_dtype: Optional[torch.dtype] = None, trainable: bool = False,
+                 spec_augment: bool = False):
         super().__init__()
         if spec_size != 256:
             raise ValueError("dg-sct_amd: HTSATFrontEnd is built for spec_size 256 (64 mel bins x 4 time quarters, every reference config)")
@@ -194,6 +244,7 @@ class HTSATFrontEnd(nn.Module):
         self.bn0 = nn.BatchNorm2d(N_MELS)
         self.patch_embed = PatchEmbed(spec_size, 4, 1, embed_dim, fused=fused, lib=lib, out_dtype=out_dtype, trainable=trainable)
         self.trainable = bool(trainable)
+        self.spec_augment = bool(spec_augment)
         self.requires_grad_(False)
         if self.trainable:
             self.bn0.requires_grad_(True)
@@ -254,7 +305,7 @@ class HTSATFrontEnd(nn.Module):
         scale = bn.weight * torch.rsqrt(var + bn.eps)
         return scale.contiguous(), (bn.bias - mean * scale).contiguous()
 
-    def _tokens_aten(self, lm: torch.Tensor) -> torch.Tensor:
+    def _tokens_aten(self, lm: torch.Tensor, stripes: Optional[torch.Tensor] = None, lam: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, T, _ = lm.shape
         bn = self.bn0
         x = lm.transpose(1, 2).unsqueeze(-1)                                   # [B, 64, T, 1] = the reference's `audio.transpose(1, 3)`
@@ -262,6 +313,12 @@ class HTSATFrontEnd(nn.Module):
             bn.num_batches_tracked += 1
         x = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, self.training, bn.momentum, bn.eps)
         x = x.transpose(1, 3)                                                  # [B, 1, T, 64]
+        if stripes is not None:                                                # `spec_augmenter` (out of place: autograd keeps the bn0 output)
+            stripes = ops.check_stripes(stripes, B, T, "HTSATFrontEnd")
+            x = x * keep_mask(stripes.to(x.device), T).unsqueeze(1).to(x.dtype)
+        if lam is not None:                                                    # `do_mixup`
+            la = lam.to(x.device).view(B, 1, 1, 1)
+            x = la * x + (1.0 - la) * torch.flip(x, [0])
         if T < MAX_FRAMES:
             x = F.interpolate(x, (MAX_FRAMES, N_MELS), mode="bicubic", align_corners=True)
         x = x.permute(0, 1, 3, 2).reshape(B, 1, N_MELS, self.freq_ratio, MAX_FRAMES // self.freq_ratio)
@@ -276,7 +333,38 @@ class HTSATFrontEnd(nn.Module):
                                "(freeze it: a name rule that unfreezes everything under 'htsat' unfreezes it too)")
         return any(p.requires_grad for p in self.parameters())
 
-    def forward(self, waveform: torch.Tensor) -> torch.Tensor:
+    def _augmentation(self, B: int, T: int, mixup_lambda, stripes):
+        """(stripes int32 [B, 4, 2] | None, lam fp32 [B] | None) of this call: both None outside train mode, as the reference applies neither
+        (`if self.htsat.training`); drawn stripes live on the CPU, where `draw_stripes` makes them.  The table is range-checked once, where it
+        is consumed: by `ops.patch_embed` on the kernel path, by `_tokens_aten` otherwise"""
+        if not self.training:
+            return None, None
+        if stripes is None and self.spec_augment:
+            stripes = draw_stripes(B, T)
+        if mixup_lambda is not None:
+            if not isinstance(mixup_lambda, torch.Tensor) or tuple(mixup_lambda.shape) != (B,) or mixup_lambda.dtype != torch.float32:
+                raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd: mixup_lambda must be an fp32 tensor [{B}], one lambda per waveform (got "
+                                   f"{tuple(getattr(mixup_lambda, 'shape', ()))} {getattr(mixup_lambda, 'dtype', type(mixup_lambda).__name__)})")
+            _refuse_grad("HTSATFrontEnd (mixup_lambda)", mixup_lambda)
+        return stripes, mixup_lambda
+
+    def _aug_through_kernels(self, waveform: torch.Tensor, kind: str) -> bool:
+        """which formulation a call with an augmentation active takes; kind: "frozen" (forward only) | "train" (with parameter gradients)"""
+        if self.fused is None and not (waveform.is_cuda and kind in _KERNELS_FASTER_AUG):
+            return False
+        if not _use_fused(self.fused, waveform, "HTSATFrontEnd"):
+            return False
+        lib = self.lib or ops._lib.default_lib()
+        if not lib.has_patch_embed_aug():
+            if self.fused:
+                raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd(fused=True) with stripes / mixup_lambda: {lib.path} does not export "
+                                   f"dgsct_patch_embed_forward_aug / dgsct_patch_embed_backward_params_aug (fused=None / False for the ATen formulation)")
+            return False
+        return True
+
+    def forward(self, waveform: torch.Tensor, mixup_lambda: Optional[torch.Tensor] = None, stripes: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mixup_lambda fp32 [B] and stripes int32 [B, 4, 2] (`draw_stripes`; None with spec_augment=True: drawn here) apply in train mode
+        only; eval mode ignores both"""
         if waveform.dim() != 2 or waveform.dtype != torch.float32:
             raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd takes an fp32 waveform [B, L] (got {tuple(waveform.shape)} {waveform.dtype})")
         _refuse_grad("HTSATFrontEnd", waveform)
@@ -288,18 +376,20 @@ class HTSATFrontEnd(nn.Module):
             raise RuntimeError(f"dg-sct_amd: HTSATFrontEnd: {L} samples give {T} frames, more than the {MAX_FRAMES} the {self.spec_size} x "
                                f"{self.spec_size} image holds (the reference's random crop_wav branch is not built)")
         out_dtype = self.out_dtype or torch.float32
+        stripes, lam = self._augmentation(B, T, mixup_lambda, stripes)
         if self._wants_grad():
-            return self._forward_trainable(waveform, B, T, out_dtype)
+            return self._forward_trainable(waveform, B, T, out_dtype, stripes, lam)
         with torch.no_grad():
-            return self._forward_frozen(waveform, B, T, out_dtype)
+            return self._forward_frozen(waveform, B, T, out_dtype, stripes, lam)
 
-    def _forward_trainable(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype) -> torch.Tensor:
+    def _forward_trainable(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype, stripes=None, lam=None) -> torch.Tensor:
         """the waveform and melW are data: the log-mel (and the statistics of bn0) are made without a graph, autograd starts at bn0"""
         melW, pe, bn = self.logmel_extractor.melW, self.patch_embed, self.bn0
-        if not _train_through_kernels(self.fused, waveform, self.lib, "HTSATFrontEnd", "audio"):
+        aug = stripes is not None or lam is not None
+        if not _train_through_kernels(self.fused, waveform, self.lib, "HTSATFrontEnd", "audio") or (aug and not self._aug_through_kernels(waveform, "train")):
             with torch.no_grad():
                 lm = self.logmel_aten(waveform)
-            return self._tokens_aten(lm).to(out_dtype)
+            return self._tokens_aten(lm, stripes, lam).to(out_dtype)
         with torch.no_grad():
             if self.training:
                 lm, mean, var = ops.logmel(waveform.contiguous(), melW, want_stats=True, lib=self.lib, ranges=self._mel_ranges())
@@ -308,11 +398,13 @@ class HTSATFrontEnd(nn.Module):
                 lm = ops.logmel(waveform.contiguous(), melW, lib=self.lib, ranges=self._mel_ranges())
                 mean, var = self._bn_statistics(None, None, B * T)
         return ops.patch_embed_train(lm, pe.proj.weight, pe.proj.bias, pe.norm.weight, pe.norm.bias, pe.norm.eps, out_dtype=out_dtype,
-                                     bn_weight=bn.weight, bn_bias=bn.bias, mean=mean, var=var, bn_eps=bn.eps, lib=self.lib)
+                                     bn_weight=bn.weight, bn_bias=bn.bias, mean=mean, var=var, bn_eps=bn.eps, lib=self.lib, stripes=stripes,
+                                     mixup_lambda=lam)
 
-    def _forward_frozen(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype) -> torch.Tensor:
-        if not _use_fused(self.fused, waveform, "HTSATFrontEnd"):
-            return self._tokens_aten(self.logmel_aten(waveform)).to(out_dtype)
+    def _forward_frozen(self, waveform: torch.Tensor, B: int, T: int, out_dtype: torch.dtype, stripes=None, lam=None) -> torch.Tensor:
+        aug = stripes is not None or lam is not None
+        if not _use_fused(self.fused, waveform, "HTSATFrontEnd") or (aug and not self._aug_through_kernels(waveform, "frozen")):
+            return self._tokens_aten(self.logmel_aten(waveform), stripes, lam).to(out_dtype)
         melW, pe = self.logmel_extractor.melW, self.patch_embed
         if self.training:
             lm, mean, var = ops.logmel(waveform.contiguous(), melW, want_stats=True, lib=self.lib, ranges=self._mel_ranges())
@@ -320,4 +412,5 @@ class HTSATFrontEnd(nn.Module):
         else:
             lm = ops.logmel(waveform.contiguous(), melW, lib=self.lib, ranges=self._mel_ranges())
             scale, shift = self._bn_affine(None, None, B * T)
-        return ops.patch_embed(lm, *pe._frozen_params(), pe.norm.eps, out_dtype=out_dtype, bn_scale=scale, bn_shift=shift, lib=self.lib)
+        return ops.patch_embed(lm, *pe._frozen_params(), pe.norm.eps, out_dtype=out_dtype, bn_scale=scale, bn_shift=shift, lib=self.lib,
+                               stripes=stripes, mixup_lambda=lam)

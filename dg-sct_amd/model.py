@@ -28,17 +28,19 @@ from .temporal import TemporalAttention
 
 
 class AVENet(nn.Module):
-    """``forward(waveform [B*T, L] fp32, frames [B, T, 3, H, W]) -> (is_event_scores [T, B, 1], event_scores [B, 28],
+    """``forward(waveform [B*T, L] fp32, frames [B, T, 3, H, W], mixup_lambda=None) -> (is_event_scores [T, B, 1], event_scores [B, 28],
     audio_visual_gate [T, B, 1], av_score [B, 28])``, the return of ``forward_swin``.
 
     ``stages``: the per-stage token counts and widths (default ``ave_stage_shapes("swinv2_base")``); ``T`` frames per clip (the reference
     hard-codes 10); ``img_size``: the frames' side, ``(img_size / 4)^2`` must be the visual token count of stage 0; ``dtype``: the trunk's
     compute dtype, the pooled features are cast to fp32 for the temporal module and the head as the reference runs them;
-    ``train_htsat=True`` keeps the audio front end and the audio side of the trunk trainable (AVS-S4's rule); ``head_fused`` is ``CMBS``'s
-    ``fused``; every other keyword goes to ``AVETrunk`` (``fused=``, ``opt=``, ``lib=``, ...)."""
+    ``train_htsat=True`` keeps the audio front end and the audio side of the trunk trainable (AVS-S4's rule); ``spec_augment=True`` is the
+    front end's: in train mode it drops the reference's SpecAugment stripes, and ``mixup_lambda`` (fp32 ``[B*T]``, ``train.mix_lambda``) mixes
+    waveform i with waveform B*T-1-i after them (net_trans.py:862-866); ``head_fused`` is ``CMBS``'s ``fused``; every other keyword goes to ``AVETrunk`` (``fused=``, ``opt=``, ``lib=``, ...)."""
 
     def __init__(self, stages: Optional[Sequence[Dict[str, int]]] = None, T: int = 10, img_size: int = 192,
-                 dtype: torch.dtype = torch.bfloat16, train_htsat: bool = False, head_fused: Optional[bool] = None, **trunk_kw):
+                 dtype: torch.dtype = torch.bfloat16, train_htsat: bool = False, head_fused: Optional[bool] = None,
+                 spec_augment: bool = False, **trunk_kw):
         super().__init__()
         stages = [dict(s) for s in (stages if stages is not None else ave_stage_shapes("swinv2_base"))]
         if (img_size // 4) ** 2 != stages[0]["Nv"] or img_size % 4:
@@ -48,19 +50,20 @@ class AVENet(nn.Module):
         self.T, self.dtype = int(T), dtype
         lib = trunk_kw.get("lib")
         self.patch_embed = PatchEmbed(img_size, in_chans=3, embed_dim=stages[0]["Cv"], out_dtype=dtype, lib=lib)
-        self.frontend = HTSATFrontEnd(embed_dim=stages[0]["Ca"], out_dtype=dtype, lib=lib, trainable=bool(train_htsat))
+        self.frontend = HTSATFrontEnd(embed_dim=stages[0]["Ca"], out_dtype=dtype, lib=lib, trainable=bool(train_htsat),
+                                      spec_augment=spec_augment)
         self.trunk = AVETrunk(stages, dtype=dtype, train_htsat=train_htsat, **trunk_kw)
         self.temporal_attn = TemporalAttention(video_dim=stages[-1]["Cv"], audio_dim=stages[-1]["Ca"], lib=lib)
         self.CMBS = CMBS(None, fused=head_fused, lib=lib)
 
-    def forward(self, waveform: torch.Tensor, frames: torch.Tensor):
+    def forward(self, waveform: torch.Tensor, frames: torch.Tensor, mixup_lambda: Optional[torch.Tensor] = None):
         if frames.dim() != 5 or frames.shape[1] != self.T:
             raise RuntimeError(f"dg-sct_amd: AVENet takes frames [B, {self.T}, 3, H, W] (got {tuple(frames.shape)})")
         bs = frames.shape[0]
         if waveform.dim() != 2 or waveform.shape[0] != bs * self.T:
             raise RuntimeError(f"dg-sct_amd: AVENet takes one waveform per frame, [{bs * self.T}, L] (got {tuple(waveform.shape)})")
         f_v = self.patch_embed(frames.reshape(bs * self.T, *frames.shape[2:]))          # 'b t c w h -> (b t) c w h'
-        f_a = self.frontend(waveform)
+        f_a = self.frontend(waveform, mixup_lambda)
         f_v, f_a, _, _ = self.trunk(f_v, f_a)                                           # [BT, 1, C] each
         f_v = f_v.float().view(bs, self.T, -1)
         f_a = f_a.float().view(bs, self.T, -1)

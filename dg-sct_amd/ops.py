@@ -898,13 +898,53 @@ def logmel(waveform: torch.Tensor, melW: torch.Tensor, want_stats: bool = False,
     return (out, stats[0], stats[1]) if want_stats else out
 
 
+def check_stripes(stripes: torch.Tensor, B: int, T: int, who: str = "check_stripes") -> torch.Tensor:
+    """a SpecAugment stripe table as the kernels take it: int32 [B, 4, 2] of half-open (begin, end), rows 0 and 1 inside the frame axis
+    [0, T], rows 2 and 3 inside the mel axis [0, 64]; begin >= end is an empty stripe.  Returns it contiguous; raises otherwise.  The C calls
+    do not read the table back (include/dgsct.h): this is where a stripe outside its axis is refused, on the host copy when there is one (a
+    table that already lives on the device is read back once)."""
+    if not isinstance(stripes, torch.Tensor) or stripes.dtype != torch.int32 or tuple(stripes.shape) != (B, 4, 2):
+        got = f"{tuple(stripes.shape)} {stripes.dtype}" if isinstance(stripes, torch.Tensor) else type(stripes).__name__
+        raise RuntimeError(f"dg-sct_amd: {who}: stripes must be an int32 tensor [{B}, 4, 2] of (begin, end) (got {got})")
+    host = stripes.detach().cpu()
+    for rows, width, axis in ((host[:, :2], T, "frame"), (host[:, 2:], N_MELS, "mel")):
+        if int(rows.min()) < 0 or int(rows.max()) > width:
+            raise RuntimeError(f"dg-sct_amd: {who}: a {axis} stripe lies outside [0, {width}] (stripes rows 0, 1: frames of the un-stretched "
+                               f"log-mel; rows 2, 3: mel bins)")
+    return stripes.contiguous()
+
+
+def _aug_operands(who: str, stripes, mixup_lambda, B: int, T: int, dev):
+    """(stripes int32 [B, 4, 2], lam fp32 [B]) on `dev`, either may be None; checked on the host before the upload"""
+    if stripes is not None:
+        stripes = check_stripes(stripes, B, T, who).to(dev)
+    if mixup_lambda is not None:
+        if not isinstance(mixup_lambda, torch.Tensor) or mixup_lambda.dtype != torch.float32 or tuple(mixup_lambda.shape) != (B,):
+            got = f"{tuple(mixup_lambda.shape)} {mixup_lambda.dtype}" if isinstance(mixup_lambda, torch.Tensor) else type(mixup_lambda).__name__
+            raise RuntimeError(f"dg-sct_amd: {who}: mixup_lambda must be an fp32 tensor [{B}], one lambda per sample (got {got})")
+        if mixup_lambda.requires_grad:
+            raise RuntimeError(f"dg-sct_amd: {who}: mixup_lambda is data and gets no gradient (detach it)")
+        mixup_lambda = mixup_lambda.to(dev).contiguous()
+    return stripes, mixup_lambda
+
+
+def _need_aug(who: str, lib: Lib):
+    if not lib.has_patch_embed_aug():
+        raise RuntimeError(f"dg-sct_amd: {who}: {lib.path} does not export dgsct_patch_embed_forward_aug / dgsct_patch_embed_backward_params_aug "
+                           f"(a library without the in-kernel augmentation; fused=False, the ATen formulation, augments without it)")
+
+
 def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor,
                 eps: float = 1e-5, out_dtype: Optional[torch.dtype] = None, bn_scale: Optional[torch.Tensor] = None,
-                bn_shift: Optional[torch.Tensor] = None, lib: Optional[Lib] = None) -> torch.Tensor:
+                bn_shift: Optional[torch.Tensor] = None, lib: Optional[Lib] = None, stripes: Optional[torch.Tensor] = None,
+                mixup_lambda: Optional[torch.Tensor] = None) -> torch.Tensor:
     """4 x 4 / stride-4 patch convolution + bias + LayerNorm in one launch -> tokens [B, (H/4) (W/4), C] (fp32 | bf16).
     Image mode (bn_scale is None): x [B, in_chans, H, W] fp32 | bf16, in_chans 1 or 3.  Audio mode (bn_scale / bn_shift [64] given): x is the
     log-mel [B, T, 64] fp32; `x * bn_scale[f] + bn_shift[f]`, the bicubic stretch of the T frames to 1024 and the fold into the 256 x 256
-    HTS-AT image are part of the kernel's loads.  weight [C, in_chans, 4, 4], bias / ln_weight / ln_bias [C] fp32; C % 32 == 0, C <= 192."""
+    HTS-AT image are part of the kernel's loads.  weight [C, in_chans, 4, 4], bias / ln_weight / ln_bias [C] fp32; C % 32 == 0, C <= 192.
+    Audio mode only: stripes (int32 [B, 4, 2], `check_stripes`) zeroes the `bn0` output inside two time and two mel stripes per sample and
+    mixup_lambda (fp32 [B]) then mixes sample b with sample B-1-b, both before the stretch and both inside the same launch
+    (dgsct_patch_embed_forward_aug); with both None the call is dgsct_patch_embed_forward as ever."""
     who = "patch_embed"
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError("dg-sct_amd: patch_embed needs CUDA/HIP tensors (no CPU fallback; PatchEmbed(fused=False) is the ATen formulation)")
@@ -920,7 +960,10 @@ def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_we
             raise RuntimeError("dg-sct_amd: patch_embed (audio): bn_scale and bn_shift go together")
         _dev_f32(who, "bn_scale", bn_scale, (N_MELS,), dev)
         _dev_f32(who, "bn_shift", bn_shift, (N_MELS,), dev)
+        stripes, mixup_lambda = _aug_operands(who, stripes, mixup_lambda, B, T, dev)
     else:
+        if stripes is not None or mixup_lambda is not None:
+            raise RuntimeError("dg-sct_amd: patch_embed: stripes / mixup_lambda belong to audio mode (image-side augmentation is not built)")
         if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or x.shape[1] not in (1, 3) or x.shape[2] % 4 or x.shape[3] % 4 \
                 or min(x.shape[2:]) < 4:
             raise RuntimeError(f"dg-sct_amd: patch_embed: x must be fp32 / bf16 [B, 1 | 3, H, W] with H, W multiples of 4 (got {tuple(x.shape)} {x.dtype})")
@@ -939,9 +982,19 @@ def patch_embed(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_we
         raise RuntimeError("dg-sct_amd: patch_embed: out_dtype must be float32 or bfloat16")
     _no_grad_inputs(who, x, weight, bias, ln_weight, ln_bias, bn_scale, bn_shift)
     lib = lib or _lib.default_lib()
+    aug = stripes is not None or mixup_lambda is not None
+    if aug:
+        _need_aug(who, lib)
     out = torch.empty(B, (H // 4) * (W // 4), C_, dtype=out_dtype, device=dev)
     code = lambda dt: _lib.F32 if dt == torch.float32 else _lib.BF16
-    _mark_stream_use(x, weight, bias, ln_weight, ln_bias, bn_scale, bn_shift)
+    _mark_stream_use(x, weight, bias, ln_weight, ln_bias, bn_scale, bn_shift, stripes, mixup_lambda)
+    if aug:
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with _dev_guard(x):
+            lib.patch_embed_forward_aug(code(out_dtype), B, T, C_, x.data_ptr(), bn_scale.data_ptr(), bn_shift.data_ptr(), ptr(stripes),
+                                        ptr(mixup_lambda), weight.data_ptr(), bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(),
+                                        float(eps), out.data_ptr(), _stream_of(x))
+        return out
     with _dev_guard(x):
         lib.patch_embed_forward(_lib.PATCH_AUDIO if audio else _lib.PATCH_IMAGE, code(x.dtype), code(out_dtype), B, in_chans, H, W, T, C_,
                                 x.data_ptr(), bn_scale.data_ptr() if audio else None, bn_shift.data_ptr() if audio else None,
@@ -955,7 +1008,7 @@ class _PatchEmbedTrainFn(torch.autograd.Function):
     convolution and the LayerNorm statistics from x -- nothing token-sized is saved"""
 
     @staticmethod
-    def forward(ctx, lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, eps, bn_eps, out_dtype):
+    def forward(ctx, lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, eps, bn_eps, out_dtype, stripes=None, lam=None):
         audio = bn_weight is not None
         scale = shift = rstd = None
         if audio:
@@ -964,15 +1017,21 @@ class _PatchEmbedTrainFn(torch.autograd.Function):
             shift = (bn_bias.detach() - mean * scale).contiguous()
             scale = scale.contiguous()
         w, b, lw, lb = weight.detach(), bias.detach(), ln_weight.detach(), ln_bias.detach()
-        out = patch_embed(x, w, b, lw, lb, eps, out_dtype, scale, shift, lib=lib)
+        if audio:
+            stripes, lam = _aug_operands("patch_embed_train", stripes, lam, x.shape[0], x.shape[1], x.device)    # (the two small tensors the backward needs again)
+        out = patch_embed(x, w, b, lw, lb, eps, out_dtype, scale, shift, lib=lib, stripes=stripes, mixup_lambda=lam)
         ctx.lib, ctx.eps, ctx.audio = lib, float(eps), audio
-        ctx.save_for_backward(x, w, b, lw, lb, *((scale, shift, mean.contiguous(), rstd) if audio else ()))
+        ctx.aug = (stripes is not None, lam is not None)
+        ctx.save_for_backward(x, w, b, lw, lb, *((scale, shift, mean.contiguous(), rstd) if audio else ()), *(t for t in (stripes, lam) if t is not None))
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, w, b, lw, lb = ctx.saved_tensors[:5]
-        scale, shift, mean, rstd = ctx.saved_tensors[5:] if ctx.audio else (None,) * 4
+        scale, shift, mean, rstd = ctx.saved_tensors[5:9] if ctx.audio else (None,) * 4
+        rest = list(ctx.saved_tensors[9:])
+        stripes = rest.pop(0) if ctx.aug[0] else None
+        lam = rest.pop(0) if ctx.aug[1] else None
         C_ = w.shape[0]
         if ctx.audio:
             B, T, in_chans, H, W = x.shape[0], x.shape[1], 1, 256, 256
@@ -988,28 +1047,36 @@ class _PatchEmbedTrainFn(torch.autograd.Function):
         ws = torch.empty(ctx.lib.patch_embed_params_ws_floats(mode, B, in_chans, H, W, C_), **f32)
         code = lambda dt: _lib.F32 if dt == torch.float32 else _lib.BF16
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _mark_stream_use(x, w, b, lw, lb, scale, shift, mean, dout)
+        _mark_stream_use(x, w, b, lw, lb, scale, shift, mean, dout, stripes, lam)
+        tail = (w.data_ptr(), b.data_ptr(), lw.data_ptr(), lb.data_ptr(), ctx.eps, dout.data_ptr(), dw.data_ptr(), db.data_ptr(), dlw.data_ptr(),
+                dlb.data_ptr(), ptr(dbn), ws.data_ptr(), _stream_of(x))
         with _dev_guard(x):
-            ctx.lib.patch_embed_backward_params(mode, code(x.dtype), code(dout.dtype), B, in_chans, H, W, T, C_, x.data_ptr(), ptr(scale), ptr(shift),
-                                                ptr(mean), w.data_ptr(), b.data_ptr(), lw.data_ptr(), lb.data_ptr(), ctx.eps, dout.data_ptr(),
-                                                dw.data_ptr(), db.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), ptr(dbn), ws.data_ptr(), _stream_of(x))
+            if stripes is not None or lam is not None:
+                ctx.lib.patch_embed_backward_params_aug(code(dout.dtype), B, T, C_, x.data_ptr(), ptr(scale), ptr(shift), ptr(mean), ptr(stripes),
+                                                        ptr(lam), *tail)
+            else:
+                ctx.lib.patch_embed_backward_params(mode, code(x.dtype), code(dout.dtype), B, in_chans, H, W, T, C_, x.data_ptr(), ptr(scale),
+                                                    ptr(shift), ptr(mean), *tail)
         need = ctx.needs_input_grad
         # the pivot of the kernel's sums is the mean bn0 normalised with: d bn0.weight = rstd g1, d bn0.bias = g0
         dbw = dbn[0] * rstd if ctx.audio and need[6] else None
         dbb = dbn[1] if ctx.audio and need[7] else None
         return (None, None, dw if need[2] else None, db if need[3] else None, dlw if need[4] else None, dlb if need[5] else None, dbw, dbb,
-                None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 def patch_embed_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ln_weight: torch.Tensor, ln_bias: torch.Tensor,
                       eps: float = 1e-5, out_dtype: Optional[torch.dtype] = None, bn_weight: Optional[torch.Tensor] = None,
                       bn_bias: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, var: Optional[torch.Tensor] = None,
-                      bn_eps: float = 1e-5, lib: Optional[Lib] = None) -> torch.Tensor:
+                      bn_eps: float = 1e-5, lib: Optional[Lib] = None, stripes: Optional[torch.Tensor] = None,
+                      mixup_lambda: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`patch_embed` for a TRAINABLE front end: the same launch forward, and weight / bias / ln_weight / ln_bias (fp32) receive fp32
     gradients from dgsct_patch_embed_backward_params (dOut fp32 or bf16, every sum in fp32, no atomics: a repeated backward is bit-identical).
     Audio mode (bn_weight, bn_bias, mean, var [64] given; x the log-mel [B, T, 64]): `bn0` enters as its own tensors, scale = bn_weight
     rsqrt(var + bn_eps) and shift = bn_bias - mean scale are formed here, and bn_weight / bn_bias receive their gradients directly (mean and
-    var -- running or batch statistics -- are functions of data and get none).  x may not require grad: no input gradient exists."""
+    var -- running or batch statistics -- are functions of data and get none).  x may not require grad: no input gradient exists.
+    stripes / mixup_lambda (audio mode, as in `patch_embed`): the forward and the backward take the *_aug exports and the recomputed convolution
+    sees the augmented pixels; both are data and get no gradient.  Both None: exactly the calls above."""
     who = "patch_embed_train"
     audio = any(t is not None for t in (bn_weight, bn_bias, mean, var))
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -1025,7 +1092,13 @@ def patch_embed_train(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
     if not lib.has_patch_embed_params():
         raise RuntimeError(f"dg-sct_amd: {who}: {lib.path} does not export dgsct_patch_embed_backward_params (a library without the front "
                            f"end's parameter gradients; fused=False, the ATen formulation, trains without it)")
-    return _PatchEmbedTrainFn.apply(lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, float(eps), float(bn_eps), out_dtype)
+    if stripes is None and mixup_lambda is None:
+        return _PatchEmbedTrainFn.apply(lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, float(eps), float(bn_eps), out_dtype)
+    if not audio:
+        raise RuntimeError(f"dg-sct_amd: {who}: stripes / mixup_lambda belong to audio mode (image-side augmentation is not built)")
+    _need_aug(who, lib)
+    return _PatchEmbedTrainFn.apply(lib, x, weight, bias, ln_weight, ln_bias, bn_weight, bn_bias, mean, var, float(eps), float(bn_eps), out_dtype,
+                                    stripes, mixup_lambda)
 
 
 # ---- patch merging between two backbone stages (csrc/pmerge.hip) ------------------------------------------------

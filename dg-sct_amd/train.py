@@ -7,6 +7,8 @@
   ``'ViT'``/``'swin'`` frozen, everything else (the HTS-AT blocks included) trains.
 * ``make_optimizer`` -- ``optim.Adam(param_group)`` + ``StepLR(step_size=decay_epoch, gamma=decay)`` (``:276-278``) with the
   values of ``AVE/train.sh`` (lr 5e-4, lr_mlp 5e-6, decay 0.35 every 3 epochs).
+* ``mix_lambda`` -- the reference's ``get_mix_lambda`` (``nets/utils.py:74-76``): the per-sample mix-up weights its launchers hand to the
+  model, drawn one at a time from numpy's global generator.
 * ``shard_clips`` / ``seed_everything`` -- per-rank sharding and seeding: the reference has one process (``--seed 43``,
   ``DataLoader(shuffle=True)``); with W ranks every rank draws the SAME epoch permutation (seed + epoch) and takes a strided
   slice of it, so the union over ranks is the single-process epoch order.
@@ -25,6 +27,7 @@ from __future__ import annotations
 import random
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 TRAIN_KEYS = ("adapter_blocks", "CMBS", "mlp_class", "temporal_attn")      # main_trans.py:242-256
@@ -80,6 +83,12 @@ def ave_loss(is_event_scores: torch.Tensor, event_scores: torch.Tensor, audio_vi
     labels_bce = labels_bce.to(is_event.dtype)
     return (F.binary_cross_entropy_with_logits(is_event, labels_bce) + F.binary_cross_entropy_with_logits(gate, labels_bce)
             + F.cross_entropy(event_scores, labels_event) + F.cross_entropy(av_score, labels_event))
+
+
+def mix_lambda(alpha: float, n: int) -> torch.Tensor:
+    """``get_mix_lambda(alpha, n)`` (``nets/utils.py:74-76``; the launchers call it with alpha 0.5): n single ``np.random.beta(alpha, alpha, 1)``
+    draws in order from numpy's global generator, as float32 ``[n]`` -- what ``HTSATFrontEnd`` / ``AVENet`` take as ``mixup_lambda``."""
+    return torch.from_numpy(np.array([np.random.beta(alpha, alpha, 1)[0] for _ in range(n)]).astype(np.float32))
 
 
 def make_optimizer(model: torch.nn.Module, lr: float = 5e-4, lr_mlp: float = 5e-6, decay: float = 0.35, decay_epoch: int = 3,

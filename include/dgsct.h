@@ -290,6 +290,23 @@ int dgsct_layer_norm_backward(int dtype, int64_t rows, int C, const void* dout, 
  *   recomputed from x: the forward stores nothing for this call.  No gradient for x.
  *   ws: dgsct_patch_embed_params_ws_floats(...) floats (one partial row per workgroup; a second launch sums the rows in a fixed order).
  *   Every output is written by the call (nothing needs zeroing), without atomics: two calls on the same inputs agree bit for bit.
+ *
+ * dgsct_patch_embed_forward_aug / dgsct_patch_embed_backward_params_aug (still DGSCT_VERSION 101, bind them by name): the audio mode of
+ * the two calls above with the reference's train-time augmentation between `bn0` and `reshape_wav2img` (net_trans.py:862-866) folded into
+ * the same loads.  H = W = 256, in_chans = 1 and the fp32 log-mel are implied; every other argument, limit and check is the sibling's, and the
+ * workspace is dgsct_patch_embed_params_ws_floats(DGSCT_PATCH_AUDIO, ...).
+ *   stripes: int32 [B][4][2] = (begin, end) half-open, `spec_augmenter` (htsat.py:451, torchlibrosa's DropStripes): rows 0 and 1 are the
+ *     time stripes of sample b, positions in the UN-stretched frame axis [0, T]; rows 2 and 3 its mel stripes in [0, 64]; begin >= end is an
+ *     empty stripe; NULL: no stripes.  bn0(lm)[b][t][f] is set to 0 inside any of the four.
+ *   lam: fp32 [B], `do_mixup` (nets/utils.py:143-153) after the stripes: x[b] <- lam[b] x[b] + (1 - lam[b]) x[B-1-b]; NULL: no mix-up.
+ *   With keep_b(t, f) = 0 inside a stripe of sample b (else 1), b' = B-1-b and the clamped bicubic taps (cf_e, i_e) of a pixel,
+ *     R = sum_e cf_e (lam_b keep_b(i_e, f) lm[b][i_e][f] + (1 - lam_b) keep_b'(i_e, f) lm[b'][i_e][f]),
+ *     K = sum_e cf_e (lam_b keep_b(i_e, f) + (1 - lam_b) keep_b'(i_e, f)),      pixel = bn_scale[f] R + bn_shift[f] K,
+ *   and dbn collects g1[f] = sum dpix (R - bn_pivot[f] K), g0[f] = sum dpix K: d bn0.bias = g0, d bn0.weight = rstd (g1 + (bn_pivot - mean) g0)
+ *   as above.  stripes and lam are data and get no gradient.  Both NULL: exactly the sibling's launches.
+ *   The stripes live in device memory, and the calls do NOT read them back to range-check them: the kernels only ever compare them with frame /
+ *   mel indices (never address with them), so a stripe outside [0, T] / [0, 64] is memory-safe and acts as its intersection with the axis.
+ *   Rejecting such a table is left to the caller that built it on the host (ops.patch_embed does).
  * Asynchronous on `stream`; 0 or an error code (dgsct_logmel_scratch_floats / dgsct_patch_embed_params_ws_floats: -1). */
 #define DGSCT_PATCH_IMAGE 0
 #define DGSCT_PATCH_AUDIO 1
@@ -306,6 +323,14 @@ int dgsct_patch_embed_backward_params(int mode, int in_dtype, int dout_dtype, in
                                       const void* dout, float* dweight /* [C][IC][4][4] */, float* dbias, float* dln_weight,
                                       float* dln_bias /* [C] */, float* dbn /* [2][64]: g1, g0; audio only, else NULL */, float* ws,
                                       void* stream);
+int dgsct_patch_embed_forward_aug(int out_dtype, int B, int T, int C, const float* logmel, const float* bn_scale, const float* bn_shift,
+                                  const int32_t* stripes /* [B][4][2] or NULL */, const float* lam /* [B] or NULL */, const float* weight,
+                                  const float* bias, const float* ln_weight, const float* ln_bias, float eps, void* out, void* stream);
+int dgsct_patch_embed_backward_params_aug(int dout_dtype, int B, int T, int C, const float* logmel, const float* bn_scale, const float* bn_shift,
+                                          const float* bn_pivot, const int32_t* stripes /* [B][4][2] or NULL */,
+                                          const float* lam /* [B] or NULL */, const float* weight, const float* bias, const float* ln_weight,
+                                          const float* ln_bias, float eps, const void* dout, float* dweight, float* dbias, float* dln_weight,
+                                          float* dln_bias, float* dbn /* [2][64]: g1, g0 */, float* ws, void* stream);
 
 /* ---- patch merging between two backbone stages (csrc/pmerge.hip) -----------------------------------------------------------------
  * The 2 x 2 merge of `f_v = my_blk.downsample(f_v)` / `f_a = htsat_blk.downsample(f_a)` (DG-SCT/AVE/nets/net_trans.py:914-916).  Optional

@@ -6,8 +6,12 @@ beside it).  Traffic floor of the audio path: waveform in, log-mel out and back 
 kernels (trainable=True, fused=True: the forward's launches + dgsct_patch_embed_backward_params) against the same module with fused=False,
 same GPU, same run, same method, and says what frontend._KERNELS_FASTER_TRAIN should hold.  Traffic floor of the backward: log-mel (or
 image) read + dOut read.
-usage: python tools/frontend_bench.py [--batch 160] [--samples 320000] [--reps 7] [--inner 5] [--embed-dim 96] [--train]
-       (profiles/frontend_bench.txt and profiles/frontend_train_bench.txt are its output)"""
+`--augment` times the audio front end in train mode with SpecAugment stripes (frontend.draw_stripes, seeded) and a mix-up lambda per
+waveform: the kernels (fused=True: dgsct_patch_embed_forward_aug, with `--train` also dgsct_patch_embed_backward_params_aug) against the
+fused=False formulation of the SAME augmentation, with the un-augmented rows of the same run beside them, and says whether
+frontend._KERNELS_FASTER_AUG should hold the kind measured ("frozen"; with `--train`: "train").
+usage: python tools/frontend_bench.py [--batch 160] [--samples 320000] [--reps 7] [--inner 5] [--embed-dim 96] [--train] [--augment]
+       (profiles/frontend_bench.txt, profiles/frontend_train_bench.txt and profiles/frontend_aug_bench.txt are its output)"""
 import argparse
 import os
 import statistics
@@ -27,6 +31,7 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--inner", type=int, default=5)
 ap.add_argument("--embed-dim", type=int, default=96)
 ap.add_argument("--train", action="store_true")
+ap.add_argument("--augment", action="store_true")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("frontend_bench: needs a GPU (a timing taken elsewhere says nothing)")
@@ -85,6 +90,52 @@ def train_rows(tag, mods, x, cot, floor_bytes):
           f"{floor_bytes / 8e6 / bwd:.3f}\n", flush=True)
     return res["fused"][2][2] < res["ATen"][2][1]
 
+
+if args.augment:
+    from dgsct_amd import frontend
+    kind = "train" if args.train else "frozen"
+    stripes = frontend.draw_stripes(B, T, generator=gen)                     # on the host, where a training step draws them
+    lam = torch.rand(B, generator=gen).to(dev)
+    print(f"augmented audio front end (2 time + 2 mel stripes per waveform, mix-up lambda per waveform; train mode), kind '{kind}': waveform "
+          f"[{B}, {L}] -> {T} frames -> tokens [{B}, 4096, {C}]; {torch.cuda.get_device_name(0)}; times in us: median (min, max) of {args.reps} "
+          f"windows of {args.inner} calls")
+    print("fused = fused=True: the *_aug exports;  ATen = the same module with fused=False (keep mask + torch.flip between bn0 and the stretch)")
+    print(f"{'tokens':<8} {'what':<8} {'augmented':<10} {'fused':>28}   {'ATen':>28}   ATen/fused")
+    wins = []
+    for out_dtype in (torch.bfloat16, torch.float32):
+        tag = "bf16" if out_dtype == torch.bfloat16 else "fp32"
+        mods = {n: HTSATFrontEnd(embed_dim=C, out_dtype=out_dtype, trainable=args.train, fused=f).to(dev).train() for n, f in (("fused", True), ("ATen", False))}
+        cot = torch.randn(B, 4096, C, generator=gen).to(dev, out_dtype)
+        res = {}
+        for aug in (False, True):
+            kw = dict(mixup_lambda=lam, stripes=stripes) if aug else {}
+            for name, m in mods.items():
+                params = [q for q in m.parameters() if q.requires_grad]
+
+                def step(m=m, params=params, kw=kw):
+                    for q in params:
+                        q.grad = None
+                    m(wave, **kw).backward(cot)
+
+                ts = [timed(lambda m=m, kw=kw: m(wave, **kw))]
+                if args.train:
+                    out = m(wave, **kw)
+                    ts += [timed(lambda out=out, params=params: torch.autograd.grad(out, params, cot, retain_graph=True)), timed(step)]
+                    del out
+                res[aug, name] = ts
+        for i, what in enumerate(("fwd", "bwd", "fwd+bwd") if args.train else ("fwd",)):
+            for aug in (False, True):
+                f, a = res[aug, "fused"][i], res[aug, "ATen"][i]
+                print(f"{tag:<8} {what:<8} {'yes' if aug else 'no':<10} {f[0]:9.1f} ({f[1]:.1f}, {f[2]:.1f})   {a[0]:9.1f} ({a[1]:.1f}, {a[2]:.1f})   "
+                      f"{a[0] / f[0]:6.2f}x", flush=True)
+        f, a = res[True, "fused"][-1], res[True, "ATen"][-1]
+        wins.append(f[2] < a[1])
+        print(f"{tag:<8} augmented / un-augmented kernels: {f[0] / res[False, 'fused'][-1][0]:.3f}\n", flush=True)
+        del mods, cot, res
+        torch.cuda.empty_cache()
+    print(f"kind '{kind}': the kernels' slowest augmented window was faster than ATen's fastest in every row (whether "
+          f"frontend._KERNELS_FASTER_AUG should hold '{kind}'): {'yes' if all(wins) else 'no'}; it holds {sorted(frontend._KERNELS_FASTER_AUG)}")
+    sys.exit(0)
 
 if args.train:
     from dgsct_amd import frontend
