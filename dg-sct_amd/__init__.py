@@ -14,3 +14,4 @@ from .frontend import HTSATFrontEnd, PatchEmbed                     # noqa: F401
 from .merging import AVETrunk, HTSATPatchMerging, SwinV2PatchMerging   # noqa: F401
 from .cmbs import CMBS                                              # noqa: F401
 from .model import AVENet                                           # noqa: F401
+from .tpavi import TPAVIModule                                      # noqa: F401

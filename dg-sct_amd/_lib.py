@@ -194,6 +194,22 @@ class Lib:
             self._cmbs_fwd.argtypes = [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 16
         if self._cmbs_bwd is not None:
             self._cmbs_bwd.argtypes = [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 23
+        # optional (include/dgsct.h): the audio-visual TPAVI block in linear form (csrc/tpavi.hip); the host emulation lacks it
+        self._tpavi_ws = getattr(c, "dgsct_tpavi_ws_bytes", None)
+        self._tpavi_sum = getattr(c, "dgsct_tpavi_frame_sum", None)
+        self._tpavi_fwd = getattr(c, "dgsct_tpavi_forward", None)
+        self._tpavi_bwd = getattr(c, "dgsct_tpavi_backward", None)
+        if self._tpavi_ws is not None:
+            self._tpavi_ws.argtypes = [C.c_int] * 5
+            self._tpavi_ws.restype = C.c_int64
+        if self._tpavi_sum is not None:
+            self._tpavi_sum.argtypes = [C.c_int] * 5 + [C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] * 2
+        if self._tpavi_fwd is not None:
+            self._tpavi_fwd.argtypes = ([C.c_int] * 5 + [C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] * 7 + [C.c_float] * 2 + [C.c_void_p] * 2
+                                        + [C.c_float] + [C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] * 3)
+        if self._tpavi_bwd is not None:
+            self._tpavi_bwd.argtypes = ([C.c_int] * 5 + [C.c_void_p] + [C.c_int64] * 3 + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p]
+                                        + [C.c_int64] * 3 + [C.c_void_p] * 2 + [C.c_int64] * 3 + [C.c_void_p] * 8)
         if c.dgsct_version() != 101:
             raise RuntimeError("dg-sct_amd: libdgsct version mismatch")
 
@@ -411,6 +427,36 @@ class Lib:
         grads = tuple(grads) if grads is not None else (None,) * 8
         self._check(self._cmbs(self._cmbs_bwd, "dgsct_cmbs_head_backward")(T, B, D, K, gamma, v, a, Wvc, Wac, wc, We, topmask, argmax, d_is, d_ev,
                                                                            d_av, dv, da, *grads, ws, stream), "dgsct_cmbs_head_backward")
+
+    def has_tpavi(self) -> bool:
+        """whether this library exports dgsct_tpavi_frame_sum / _forward / _backward / _ws_bytes (csrc/tpavi.hip)"""
+        return None not in (self._tpavi_ws, self._tpavi_sum, self._tpavi_fwd, self._tpavi_bwd)
+
+    def _tpavi(self, fn, name: str):
+        if fn is None:
+            raise RuntimeError(f"dg-sct_amd: {self.path} does not export {name} (a library without the TPAVI kernels)")
+        return fn
+
+    def tpavi_ws_bytes(self, B: int, C_: int, T: int, H: int, W: int) -> int:
+        n = self._tpavi(self._tpavi_ws, "dgsct_tpavi_ws_bytes")(B, C_, T, H, W)
+        if n < 0:
+            raise RuntimeError(f"dgsct_tpavi_ws_bytes failed: {self.c.dgsct_last_error().decode()}")
+        return int(n)
+
+    def tpavi_frame_sum(self, dims, x, xs, s, stream):
+        """dims (B, C, T, H, W); xs the element strides of (b, c, t); pointers as ints (include/dgsct.h: dgsct_tpavi_frame_sum)"""
+        self._check(self._tpavi(self._tpavi_sum, "dgsct_tpavi_frame_sum")(*dims, x, *xs, s, stream), "dgsct_tpavi_frame_sum")
+
+    def tpavi_forward(self, dims, x, xs, A, c, mu0, bn_w, bn_b, run_mean, run_var, momentum, bn_eps, ln_w, ln_b, ln_eps, z, zs, stat, ws, stream):
+        """mu0 None: no BatchNorm inside (eval: the caller folded it into A, c); then bn_*, run_*, stat, ws may be None
+        (include/dgsct.h: dgsct_tpavi_forward)"""
+        self._check(self._tpavi(self._tpavi_fwd, "dgsct_tpavi_forward")(*dims, x, *xs, A, c, mu0, bn_w, bn_b, run_mean, run_var, momentum, bn_eps,
+                                                                        ln_w, ln_b, ln_eps, z, *zs, stat, ws, stream), "dgsct_tpavi_forward")
+
+    def tpavi_backward(self, dims, x, xs, A, c, stat, bn_w, bn_b, ln_w, ln_eps, dz, gs, ds, dx, dxs, dA, dc, dbn_w, dbn_b, dln_w, dln_b, ws, stream):
+        """stat None: no BatchNorm inside; then bn_*, dbn_* may be None; ds may be None (include/dgsct.h: dgsct_tpavi_backward)"""
+        self._check(self._tpavi(self._tpavi_bwd, "dgsct_tpavi_backward")(*dims, x, *xs, A, c, stat, bn_w, bn_b, ln_w, ln_eps, dz, *gs, ds, dx, *dxs,
+                                                                         dA, dc, dbn_w, dbn_b, dln_w, dln_b, ws, stream), "dgsct_tpavi_backward")
 
     def layer_norm_forward(self, dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream):
         self._check(self.c.dgsct_layer_norm_forward(dtype, rows, C_, x, w, b, eps, residual, out, mu, rstd, stream), "dgsct_layer_norm_forward")

@@ -1351,3 +1351,169 @@ def cmbs_head(v: torch.Tensor, a: torch.Tensor, video_cas_w, video_cas_b, audio_
             raise RuntimeError(f"dg-sct_amd: cmbs_head: {name} must hold {n} elements on {v.device} for D = {v.shape[-1]}, K = {K}")
     outs = _CMBSHeadFn.apply(lib, float(gamma), v, a, video_cas_w, video_cas_b, audio_cas_w, audio_cas_b, cls_w, cls_b, event_w, event_b)
     return outs if return_saved else outs[:3]
+
+
+# ---- the audio-visual TPAVI block in linear form (csrc/tpavi.hip) ------------------------------------------------------------------
+TPAVI_MIN_C, TPAVI_MAX_C, TPAVI_MAX_T = 64, 256, 16
+
+
+def _tpavi_view(x: torch.Tensor, T: Optional[int]):
+    """x [B, C, T, H, W] or frames [B*T, C, H, W] -> (x with contiguous planes, (B, C, T, H, W), element strides of (b, c, t)): what the
+    kernels address.  Copies only if a plane's H*W positions are not contiguous."""
+    if x.dim() == 5:
+        B, C_, T_, H, W = x.shape
+        if not (x.stride(4) == 1 and x.stride(3) == W):
+            x = x.contiguous()
+        return x, (B, C_, T_, H, W), (x.stride(0), x.stride(1), x.stride(2))
+    BT, C_, H, W = x.shape
+    if not (x.stride(3) == 1 and x.stride(2) == W):
+        x = x.contiguous()
+    return x, (BT // T, C_, T, H, W), (T * x.stride(0), x.stride(1), x.stride(0))
+
+
+def tpavi_setup(s, audio, align_w, align_b, g_w, g_b, wz_w, wz_b, theta_w, theta_b, phi_w, phi_b, HW: int):
+    """The per-clip setup of the linear form, plain torch under autograd: frame sums ``s [B, T, C]`` and
+    ``audio [B, T, 128]`` -> ``(A [B, C, C], c [B, C], audio_temp [B, T, C])`` with ``u = A_b x_p + c_b`` the block's value in front of
+    its BatchNorm.  The 1x1x1 convolutions' weights come as stored (5-D)."""
+    T = s.shape[1]
+    Wg, Wz, Wt, Wp = (w.flatten(1) for w in (g_w, wz_w, theta_w, phi_w))
+    a = torch.nn.functional.linear(audio, align_w, align_b)                  # [B, T, C]   (the module's second result)
+    phi = torch.nn.functional.linear(a, Wp, phi_b)                           # [B, T, Ci]
+    gbar = torch.nn.functional.linear(s, Wg) + HW * g_b                      # [B, T, Ci]
+    K = torch.matmul(phi.transpose(1, 2), gbar) / (T * HW)                   # [B, Ci, Ci]
+    WK = torch.matmul(Wz, K.transpose(1, 2))                                 # [B, C, Ci]
+    return torch.matmul(WK, Wt), torch.matmul(WK, theta_b) + wz_b, a
+
+
+class _TPAVISumFn(torch.autograd.Function):
+    """x -> frame sums s [B, T, C] (one launch).  The backward hands autograd the broadcast of ds as an expanded view: its accumulation
+    into dx is the extra pass."""
+
+    @staticmethod
+    def forward(ctx, lib, x, T):
+        x, dims, xs = _tpavi_view(x, T)
+        B, C_, T_ = dims[:3]
+        s = torch.empty(B, T_, C_, dtype=torch.float32, device=x.device)
+        _mark_stream_use(x)
+        with _dev_guard(x):
+            lib.tpavi_frame_sum(dims, x.data_ptr(), xs, s.data_ptr(), _stream_of(x))
+        ctx.dims, ctx.five = dims, x.dim() == 5
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        B, C_, T_, H, W = ctx.dims
+        if ctx.five:
+            return None, ds.permute(0, 2, 1)[:, :, :, None, None].expand(B, C_, T_, H, W), None
+        return None, ds.reshape(B * T_, C_)[:, :, None, None].expand(B * T_, C_, H, W), None
+
+
+class _TPAVIFn(torch.autograd.Function):
+    """(x, A, c, bn_w, bn_b, ln_w, ln_b) -> z = LayerNorm_C(BatchNorm(A_b x + c_b) + x).  ``mu0`` None: no BatchNorm inside (eval: folded
+    into A, c by the caller).  Forward: two passes over x and a finalising launch (one pass without BatchNorm); backward: three passes and
+    three reductions.  Saves x, A, c and the [2, C] statistics: nothing else of x's size."""
+
+    @staticmethod
+    def forward(ctx, lib, T, x, A, c, bn_w, bn_b, ln_w, ln_b, mu0, run_mean, run_var, momentum, bn_eps, ln_eps):
+        x, dims, xs = _tpavi_view(x, T)
+        C_ = dims[1]
+        dev = x.device
+        z = torch.empty_like(x)
+        z, _, zs = _tpavi_view(z, T)
+        A, c = A.contiguous(), c.contiguous()
+        ln_w, ln_b = ln_w.detach().contiguous(), ln_b.detach().contiguous()
+        stat = ws = None
+        if mu0 is not None:
+            bn_w, bn_b = bn_w.detach().contiguous(), bn_b.detach().contiguous()
+            stat = torch.empty(2, C_, dtype=torch.float32, device=dev)
+            ws = torch.empty(2048 * C_, dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        _mark_stream_use(x, A, c, ln_w, ln_b, *[t for t in (bn_w, bn_b, mu0, run_mean, run_var) if t is not None])
+        with _dev_guard(x):
+            lib.tpavi_forward(dims, x.data_ptr(), xs, A.data_ptr(), c.data_ptr(), ptr(mu0), ptr(bn_w) if stat is not None else None,
+                              ptr(bn_b) if stat is not None else None, ptr(run_mean), ptr(run_var), float(momentum), float(bn_eps),
+                              ln_w.data_ptr(), ln_b.data_ptr(), float(ln_eps), z.data_ptr(), zs, ptr(stat), ptr(ws), _stream_of(x))
+        ctx.lib, ctx.T, ctx.dims, ctx.ln_eps, ctx.bn = lib, T, dims, float(ln_eps), stat is not None
+        ctx.save_for_backward(x, A, c, ln_w, *((stat, bn_w, bn_b) if stat is not None else ()))
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, A, c, ln_w, *bn = ctx.saved_tensors
+        stat, bn_w, bn_b = bn if ctx.bn else (None, None, None)
+        lib, dims = ctx.lib, ctx.dims
+        B, C_ = dims[:2]
+        dev = x.device
+        x, _, xs = _tpavi_view(x, ctx.T)
+        dz, _, gs = _tpavi_view(dz.float(), ctx.T)
+        dx = torch.empty_like(x)
+        dx, _, dxs = _tpavi_view(dx, ctx.T)
+        f32 = dict(dtype=torch.float32, device=dev)
+        dA, dc = torch.empty(B, C_, C_, **f32), torch.empty(B, C_, **f32)
+        dln_w, dln_b = torch.empty(C_, **f32), torch.empty(C_, **f32)
+        dbn_w, dbn_b = (torch.empty(C_, **f32), torch.empty(C_, **f32)) if ctx.bn else (None, None)
+        ws = torch.empty(lib.tpavi_ws_bytes(*dims), dtype=torch.uint8, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        _mark_stream_use(x, A, c, ln_w, dz, *[t for t in (stat, bn_w, bn_b) if t is not None])
+        with _dev_guard(x):
+            lib.tpavi_backward(dims, x.data_ptr(), xs, A.data_ptr(), c.data_ptr(), ptr(stat), ptr(bn_w), ptr(bn_b), ln_w.data_ptr(), ctx.ln_eps,
+                               dz.data_ptr(), gs, None, dx.data_ptr(), dxs, dA.data_ptr(), dc.data_ptr(), ptr(dbn_w), ptr(dbn_b),
+                               dln_w.data_ptr(), dln_b.data_ptr(), ws.data_ptr(), _stream_of(x))
+        return None, None, dx, dA, dc, dbn_w, dbn_b, dln_w, dln_b, None, None, None, None, None, None
+
+
+def tpavi_supported(x: torch.Tensor, audio: torch.Tensor, T: Optional[int] = None) -> bool:
+    """the kernels take these inputs: fp32 ``x [B, C, T, H, W]`` (or frames ``[B*T, C, H, W]`` with ``T``) and ``audio [B, T, 128]`` on one
+    ROCm device, inside the limits of include/dgsct.h"""
+    if not (isinstance(x, torch.Tensor) and isinstance(audio, torch.Tensor) and x.dim() in (4, 5) and audio.dim() == 3):
+        return False
+    if x.dim() == 4 and (not T or x.shape[0] % T):
+        return False
+    B, C_, T_ = (x.shape[0], x.shape[1], x.shape[2]) if x.dim() == 5 else (x.shape[0] // T, x.shape[1], T)
+    return (x.is_cuda and audio.device == x.device and x.dtype == torch.float32 and audio.dtype == torch.float32 and B >= 1
+            and tuple(audio.shape[:2]) == (B, T_) and C_ % 64 == 0 and TPAVI_MIN_C <= C_ <= TPAVI_MAX_C and 1 <= T_ <= TPAVI_MAX_T
+            and x.shape[-1] >= 1 and x.shape[-2] >= 1)
+
+
+def tpavi(x: torch.Tensor, audio: torch.Tensor, align_w, align_b, g_w, g_b, wz_w, wz_b, theta_w, theta_b, phi_w, phi_b, bn_w, bn_b,
+          run_mean, run_var, ln_w, ln_b, training: bool, T: Optional[int] = None, momentum: float = 0.1, bn_eps: float = 1e-5,
+          ln_eps: float = 1e-5, lib: Optional[Lib] = None):
+    """``TPAVIModule.forward`` (mode 'dot', audio branch, BatchNorm layer) through the kernels of csrc/tpavi.hip: returns
+    ``(z, audio_temp)``, ``z`` in ``x``'s shape and layout.  ``x`` is ``[B, C, T, H, W]``, or the model's frames ``[B*T, C, H, W]`` with
+    ``T`` given; neither is copied.  The per-clip setup (``tpavi_setup``) runs in torch under autograd, so the gradients of ``theta``,
+    ``phi``, ``g``, ``W_z.0``, ``align_channel`` and ``audio`` come from its backward; the passes over ``x`` are the kernels.
+    ``training``: batch statistics, and ``run_mean`` / ``run_var`` are updated in place (the caller counts ``num_batches_tracked``);
+    otherwise the BatchNorm is folded into ``A`` and ``c`` here.  Inputs outside the limits raise; there is no CPU path."""
+    if not (isinstance(x, torch.Tensor) and x.dim() in (4, 5) and isinstance(audio, torch.Tensor)):
+        raise RuntimeError("dg-sct_amd: tpavi takes x [B, C, T, H, W] or frames [B*T, C, H, W] with T, and audio [B, T, 128]")
+    if x.dtype != torch.float32 or audio.dtype != torch.float32:
+        raise RuntimeError(f"dg-sct_amd: tpavi runs in fp32 (got {x.dtype}, {audio.dtype})")
+    if lib is None:
+        if not x.is_cuda:
+            raise RuntimeError("dg-sct_amd: tpavi runs on MI355X through libdgsct.so; there is no CPU path (TPAVIModule(fused=False) is the "
+                               "ATen linear form)")
+        lib = _lib.default_lib()
+    if not lib.has_tpavi():
+        raise RuntimeError(f"dg-sct_amd: {lib.path} does not export dgsct_tpavi_forward (a library without the TPAVI kernels)")
+    if x.dim() == 4 and (not T or x.shape[0] % T):
+        raise RuntimeError(f"dg-sct_amd: tpavi on frames {list(x.shape)} needs T dividing the first dimension (got T={T})")
+    if x.dim() == 4:
+        audio = audio.reshape(-1, T, audio.shape[-1])
+    if not tpavi_supported(x, audio, T):
+        raise RuntimeError(f"dg-sct_amd: tpavi: the kernels take fp32 x with C a multiple of 64 in [{TPAVI_MIN_C}, {TPAVI_MAX_C}] and "
+                           f"1 <= T <= {TPAVI_MAX_T}, and audio [B, T, 128] on the same ROCm device (got x {list(x.shape)}, audio "
+                           f"{list(audio.shape)} on {x.device})")
+    T5 = T if x.dim() == 4 else None
+    xv, dims, _ = _tpavi_view(x, T5)
+    B, C_, T_, H, W = dims
+    s = _TPAVISumFn.apply(lib, xv, T5)
+    A, c, a_temp = tpavi_setup(s, audio, align_w, align_b, g_w, g_b, wz_w, wz_b, theta_w, theta_b, phi_w, phi_b, H * W)
+    if training:
+        with torch.no_grad():                              # the shift of the centred variance accumulation: mean of u from the frame sums
+            mu0 = ((torch.bmm(A, s.sum(1)[:, :, None])[:, :, 0] + T_ * H * W * c).sum(0) / (B * T_ * H * W)).contiguous()
+        z = _TPAVIFn.apply(lib, T5, xv, A, c, bn_w, bn_b, ln_w, ln_b, mu0, run_mean, run_var, momentum, bn_eps, ln_eps)
+    else:
+        k = bn_w * torch.rsqrt(run_var + bn_eps)
+        z = _TPAVIFn.apply(lib, T5, xv, k[None, :, None] * A, k * (c - run_mean) + bn_b, None, None, ln_w, ln_b, None, None, None, momentum,
+                           bn_eps, ln_eps)
+    return z, a_temp

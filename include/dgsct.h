@@ -404,6 +404,34 @@ int dgsct_cmbs_head_backward(int T, int B, int D, int K, float gamma, const floa
                              const float* d_ev, const float* d_av, float* dv, float* da, float* dWvc, float* dbvc, float* dWac, float* dbac,
                              float* dwc, float* dbc, float* dWe, float* dbe, void* ws, void* stream);
 
+/* ---- the audio-visual TPAVI block in linear form (csrc/tpavi.hip; DG-SCT/AVS/avs_scripts/avs_s4/model/TPAVI.py, mode 'dot') --------
+ * Optional exports, like the event head's (still DGSCT_VERSION 101): bind them by name.  Everything fp32.
+ * The caller owns the per-clip setup (A [B][C][C], c [B][C]); these are the passes over x:
+ *   u = A_b x_p + c_b;   v = BatchNorm3d(u) with batch statistics over B, T, H, W;   z = LayerNorm_C(v + x) * ln_w + ln_b
+ * x, z, dz, dx are addressed as base + b*sb + c*sc + t*st + (h*W + w): element strides of (b, c, t), the H*W positions of a plane
+ * contiguous, no alignment needed.  [B][C][T][H][W] is (C*T*H*W, T*H*W, H*W); [B*T][C][H][W] is (T*C*H*W, H*W, C*H*W).
+ * frame_sum: s [B][T][C] = sum over h, w of x.
+ * forward: mu0 [C] non-NULL selects the train-mode BatchNorm; it is the caller's mean of u over B, T, H, W (from the frame sums), used as
+ *   the shift of the centred variance accumulation; the kernels recompute the mean.  stat [2][C] receives mean | 1/sqrt(var + bn_eps);
+ *   run_mean / run_var (each may be NULL) are updated as nn.BatchNorm3d does (unbiased variance).  mu0 NULL: no BatchNorm (eval mode:
+ *   fold it into A and c); bn_w, bn_b, run_*, stat and ws may then be NULL.
+ * backward: stat as written by the forward (NULL: no BatchNorm; bn_w, bn_b, dbn_w, dbn_b may then be NULL).  ds [B][T][C] (may be
+ *   NULL) is the cotangent of the frame sums, added to dx.  dx, dA [B][C][C], dc [B][C], dbn_w, dbn_b, dln_w, dln_b [C] are OVERWRITTEN.
+ *   dx may not alias dz.  Every reduction is partial rows in `ws` (dgsct_tpavi_ws_bytes(...) bytes; the forward uses its first 2048 * C) summed in
+ *   a fixed order: no atomics, results are bit-identical from call to call.
+ * Limits: C a multiple of 64, 64 <= C <= 256; 1 <= T <= 16; B, H, W >= 1; A 16-byte aligned.
+ * Asynchronous on `stream`; 0 or an error code (dgsct_tpavi_ws_bytes: -1). */
+int64_t dgsct_tpavi_ws_bytes(int B, int C, int T, int H, int W);
+int dgsct_tpavi_frame_sum(int B, int C, int T, int H, int W, const float* x, int64_t xb, int64_t xc, int64_t xt, float* s, void* stream);
+int dgsct_tpavi_forward(int B, int C, int T, int H, int W, const float* x, int64_t xb, int64_t xc, int64_t xt, const float* A, const float* c,
+                        const float* mu0, const float* bn_w, const float* bn_b, float* run_mean, float* run_var, float momentum, float bn_eps,
+                        const float* ln_w, const float* ln_b, float ln_eps, float* z, int64_t zb, int64_t zc, int64_t zt, float* stat, void* ws,
+                        void* stream);
+int dgsct_tpavi_backward(int B, int C, int T, int H, int W, const float* x, int64_t xb, int64_t xc, int64_t xt, const float* A, const float* c,
+                         const float* stat, const float* bn_w, const float* bn_b, const float* ln_w, float ln_eps, const float* dz, int64_t gb,
+                         int64_t gc, int64_t gt, const float* ds, float* dx, int64_t db, int64_t dcs, int64_t dt, float* dA, float* dc,
+                         float* dbn_w, float* dbn_b, float* dln_w, float* dln_b, void* ws, void* stream);
+
 /* Per-frame scalar gate on a feature block: the tail of the AVVP / AVS copies of TemporalAttention
  * (`x + gate * x * gamma` with one gate per frame: AVVP/nets/mgn.py:155-156 on [B*10][128] features,
  * avs_s4/model/PVT_AVSModel.py:572-577 on the four [B*5][256][H][W] decoder maps).
